@@ -19,10 +19,14 @@ poses/queries (weak scaling, no data-path collective); value = all ranks' cycles
 without torchrun, the parent spawns the N ranks itself (before anything touches a GPU) and exits with
 their status; under `torch.distributed.run` (RANK/WORLD_SIZE set) WORLD_SIZE must equal --gpus.
 
-Prints ONE JSON line on rank 0 (see the task contract) including
-  roofline:      dominant kernel (astar_search) algorithmic GB/s vs the 8 TB/s HBM peak
-  roofline_rows: the same for himm_raster and vfh_step, from the same run
+Prints ONE JSON line on rank 0 (see the task contract).  A plain run sets up, warms up, times --steps steps, writes the last
+step's outputs when --dump-outputs DIR is given, and prints the line (metric, value, unit, ms_per_step, config).  --full
+adds everything else the bench measures or checks, after the timed region unless noted:
+  roofline:      dominant kernel (astar_search) algorithmic GB/s vs the 8 TB/s HBM peak (its launches are bracketed by
+                 events inside the timed region)
+  roofline_rows: the same for himm_raster and vfh_step, from one profiled turn of the pipeline
   cpu_baseline:  the CPU oracle ("port") timed on a bounded sample of the same workload
+  paths_checked: one batch of the loop path for path against the oracle (--check-paths asks for it in a plain run too)
 """
 import argparse
 import json
@@ -73,12 +77,20 @@ def parse():
                          "GPU_MAX_HW_QUEUES=8, set above: with the runtime's default of 4 queues the rate collapses).  "
                          "Every launch is stretched by the ones it overlaps with, and "
                          "the roofline line divides by that per-launch duration")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-check-paths", action="store_true", help="skip the path check that is the default on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline figure: the search kernel's event brackets in the "
+                         "timed region and one profiled turn after it (roofline, roofline_rows, kernel_ms_per_pass), E per query "
+                         "set and the job counters (work_inflation), the path check and the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all; fixed seeded samples of the paths and of the map layers)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-check-paths", action="store_true", help="skip the path check that is the default of --full on one GPU")
     ap.add_argument("--check-paths", action="store_true",
-                    help="(default at --gpus 1, so that the driver's own record is path-certified; about 2 s on the box's host "
-                         "cores, outside the timed region) after the timed region: the LAST batch of one more turn of the pipeline (searched while the turn's other "
+                    help="(default of --full at --gpus 1, so that a full record is path-certified; about 2 s on the box's host "
+                         "cores, outside the timed region) after the timed region: the LAST batch of the last turn of the pipeline (with --full, of "
+                         "the profiled turn after the timed region; searched while the turn's other "
                          "batches are in flight) is handed to the CPU oracle -- status, cost, length and every cell of every path "
                          "of its queries against the map that batch saw (`config.paths_checked`; a mismatch ends the run)")
     ap.add_argument("--tiled-full-gather", action="store_true", help="--tiled: all-gather whole windows instead of dirty tiles")
@@ -435,10 +447,64 @@ def work_inflation(args, world, settled_per_launch, counters, passes):
         return out or None
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_SEED = 20261016            # the samples below are the same in every run with the same arguments
+DUMP_PATHS = 256                # (pass, query) pairs of the last step whose paths are written
+DUMP_MAP_CELLS = 1 << 20        # cells of each map layer written
+
+
+def last_step_outputs(e, R, args, nq, step_no, n_out, d_results, d_paths, d_vfh_out, only_astar):
+    """What the timed path handed its caller in the last step (the last --pipeline passes; read after e.synchronize()), as
+    float64 / float32 arrays by name: status, length and cost of every A* query of the step, (pass, query); the paths of a
+    fixed seeded sample of its (pass, query) pairs, concatenated, with (pass, query, offset, cells) per pair; the VFH+ commands
+    of its last pass; a fixed seeded sample of the master and laser layers' cells as the step left them."""
+    import numpy as np
+    passes = list(range(max(0, step_no - args.pipeline), step_no))
+    res = np.stack([d_results[i % n_out].cpu().numpy().reshape(nq, 6) for i in passes])
+    # (the record's other fields -- expanded, rounds, buckets -- count the asynchronous scheduler's work and vary from run to run)
+    out = {"astar_" + f: res[:, :, i].astype(np.float64) for i, f in enumerate(("status", "path_len", "cost"))}
+    rng = np.random.default_rng(DUMP_SEED)
+    cells_left = (DUMP_LIMIT_BYTES // 2) // 8       # the sampled paths take at most half of the budget
+    pairs = np.sort(rng.choice(len(passes) * nq, size=min(DUMP_PATHS, len(passes) * nq), replace=False))
+    index, paths, offset = [], [], 0
+    for pq in pairs.tolist():
+        p, q = divmod(pq, nq)
+        cells = min(int(res[p, q, 1]), args.max_path, cells_left - offset) if res[p, q, 0] == 0 else 0
+        if cells > 0:
+            paths.append(d_paths[passes[p] % n_out].view(nq, args.max_path)[q, :cells].cpu().numpy())
+        index.append((p, q, offset, max(cells, 0)))
+        offset += max(cells, 0)
+    out["astar_paths_sample"] = np.concatenate(paths).astype(np.float64) if paths else np.zeros(0, np.float64)
+    out["astar_paths_sample_index"] = np.array(index, np.float64).reshape(-1, 4)
+    if not only_astar:
+        vfh = d_vfh_out.cpu().numpy().view(R.capi.VFH_OUT_DTYPE)
+        for field in R.capi.VFH_OUT_DTYPE.names:
+            out["vfh_" + field] = vfh[field].astype(np.float64)
+    cells = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(e.ncell, size=min(DUMP_MAP_CELLS, e.ncell), replace=False))
+    for name, layer in (("map_master_sample", R.capi.LAYER_MASTER), ("map_laser_sample", R.capi.LAYER_LASER)):
+        out[name] = np.ascontiguousarray(e.download(layer)[cells], dtype=np.float32)
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: DIR/<name>.npy for every array (float32 / float64 only, DUMP_LIMIT_BYTES in all)"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    bad = [k for k, a in arrays.items() if a.dtype not in (np.float32, np.float64)]
+    if bad or total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %s" % ("not float32 / float64: %s" % bad if bad else "%d bytes > %d" % (total, DUMP_LIMIT_BYTES)))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": len(arrays), "bytes": int(total)}
+
+
 def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     # developer switch: RNA_BENCH_FORCE_SPAWN=1 takes the spawn path (parent -> Popen -> rank -> RCCL init -> barriers ->
     # max over ranks) with a single rank too, so that the code an N-GPU run takes can run on a one-GPU box
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or os.environ.get("RNA_BENCH_FORCE_SPAWN") == "1"):
@@ -616,14 +682,16 @@ def main():
     torch.cuda.synchronize()
     check_results("during warm-up")
 
-    # HIP events bracket the dominant kernel (the A* search, on its stage's own stream) in the timed region.  The other
+    # --full: HIP events bracket the dominant kernel (the A* search, on its stage's own stream) in the timed region.  The other
     # kernels all run on the engine stream, whose chain of short dependent kernels gates the next batch: an event record
     # is a packet of its own there (about 35 us each in the loop, ~1 ms per pass for the ten slots), so they are
     # bracketed in one extra turn of the pipeline AFTER the timed region instead (`kernel_ms_per_pass`, `roofline_rows`).
-    e.profile(2)
-    e.profile_reset()
+    if args.full:
+        e.profile(2)
+        e.profile_reset()
+        if step_no[0]:   # (without a warm-up no stage is allocated yet, and the counters start at zero)
+            e.astar_job_counters(reset=True)   # (waits for the warm-up's searches; the timed region's jobs are read after it)
     xfer[0] = xfer[1] = 0
-    e.astar_job_counters(reset=True)   # (waits for the warm-up's searches; the timed region's jobs are read after it)
     if host_t is not None:
         host_t[:] = [0.0, 0.0, 0.0, 0]
     barrier()
@@ -637,24 +705,30 @@ def main():
     elapsed = time.perf_counter() - t0
     host_cores_used = (time.process_time() - cpu0) / max(elapsed, 1e-9)   # CPU seconds of ALL the process's threads per wall second
     barrier()
-    prof = e.profile_get()
-    e.profile(False)
-    job_counters = e.astar_job_counters(reset=True)
+    # what the timed path handed its caller in the last step, read before anything else runs on the engine
+    outputs = last_step_outputs(e, R, args, nq, step_no[0], n_out, d_results, d_paths, d_vfh_out, only_astar) \
+        if args.dump_outputs and rank == 0 else None
+    if args.full:
+        prof = e.profile_get()
+        e.profile(False)
+        job_counters = e.astar_job_counters(reset=True)
     host_t_timed = list(host_t) if host_t is not None else None
     found, answered, total = check_results("in the timed region")
     xfer_timed = list(xfer)
-    e.profile(1)
-    e.profile_reset()
-    step()
-    e.synchronize()
-    torch.cuda.synchronize()
-    prof_all = e.profile_get()
-    e.profile(False)
-    check_results("in the profiled turn after the timed region")
+    if args.full:
+        e.profile(1)
+        e.profile_reset()
+        step()
+        e.synchronize()
+        torch.cuda.synchronize()
+        prof_all = e.profile_get()
+        e.profile(False)
+        check_results("in the profiled turn after the timed region")
     xfer[0], xfer[1] = xfer_timed
     paths_checked = None
-    if (args.check_paths or (world == 1 and not args.no_check_paths)) and layout is None:
-        # the profiled turn's last pass: no map update has followed it, so the master layer is the map its snapshot saw
+    if (args.check_paths or (args.full and world == 1 and not args.no_check_paths)) and layout is None:
+        # the last pass (of the profiled turn with --full, else of the timed region): no map update has followed it, so the
+        # master layer is the map its snapshot saw
         b_last, k_last = (step_no[0] - 1) % n_out, (step_no[0] - 1) % ROTATE
         paths_checked = check_paths(e.download(R.capi.LAYER_MASTER), query_sets[k_last],
                                     d_results[b_last].cpu().numpy().reshape(nq, 6),
@@ -663,13 +737,14 @@ def main():
             raise SystemExit("--check-paths: %d of %d queries of the checked batch differ from the oracle"
                              % (paths_checked["queries"] - paths_checked["matched"], paths_checked["queries"]))
 
-    # E per query set (settled cells, from the pages still resident after a launch), on the map as the timed region left it
-    settled_sets = []
-    for k in range(ROTATE):
-        e.astar_device(d_queries[k].data_ptr(), nq, d_paths[0].data_ptr(), args.max_path, d_results[0].data_ptr())
-        e.synchronize()
-        settled_sets.append(float(e.astar_settled(nq).astype(np.int64).sum()))
-    settled_per_launch = float(np.mean(settled_sets))
+    if args.full:
+        # E per query set (settled cells, from the pages still resident after a launch), on the map as the timed region left it
+        settled_sets = []
+        for k in range(ROTATE):
+            e.astar_device(d_queries[k].data_ptr(), nq, d_paths[0].data_ptr(), args.max_path, d_results[0].data_ptr())
+            e.synchronize()
+            settled_sets.append(float(e.astar_settled(nq).astype(np.int64).sum()))
+        settled_per_launch = float(np.mean(settled_sets))
 
     t_max = D.max_over_ranks(elapsed, "cpu" if share else dev) if use_dist else elapsed
     # every rank's shard of the global batch and the cycles it served in the timed region, for the line rank 0 prints
@@ -688,22 +763,7 @@ def main():
         passes = args.steps * args.pipeline
         cycles = sum(r[2] for r in shard_rows)      # all ranks' cycles (= queries x world x passes)
         assert cycles == args.queries * world * passes
-        ms_search = prof["astar_search"][0] / max(1, prof["astar_search"][1])
-        alg_bytes = settled_per_launch * ASTAR_BYTES_PER_SETTLED
-        achieved = alg_bytes / (ms_search * 1e-3) / 1e9 if ms_search > 0 else 0.0
-        traffic, traffic_src = pmc_traffic("rna::tsa_search_kernel", args, world)
         wall_per_pass = t_max / passes
-
-        def row(kernel_key, pmc_name, alg):
-            ms = prof_all[kernel_key][0] / max(1, prof_all[kernel_key][1])
-            gbs = alg / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-            tr, src = pmc_traffic(pmc_name, args, world)
-            return {"kernel": pmc_name if isinstance(pmc_name, str) else " + ".join(pmc_name), "bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
-                    "traffic": tr, "traffic_source": src, "algorithmic_bytes_per_launch": alg, "avg_launch_ms": ms,
-                    "launches": prof_all[kernel_key][1], "measured": "one turn of the pipeline after the timed region"}
-
-        himm_alg = float(np.mean([(8.0 * np.hypot(r["ex"] - r["sx"], r["ey"] - r["sy"]) / 0.05 + 8.0 * (r["clear_end"] == 0) + 40.0).sum()
-                                  for r in ray_sets]))
         out = {
             "metric": ("replan cycles/sec (HIMM+VFH++A*) on %dx%d grid" if not only_astar else "DEVELOPER RUN, A* only, not the metric (%dx%d grid)") % (n, n),
             "value": cycles / t_max, "unit": "replan cycles/s", "n_gpus": world, "steps": args.steps,
@@ -732,46 +792,75 @@ def main():
                                     if "RNA_BENCH_PARENT" in os.environ else {"spawned_by_bench": False}),
                        "parallelism": ("query-sharded x%d" % world) if layout is None else
                                       ("one map tiled %d x %d (windowed HIMM, %d-cell halo exchange, all-gather of owner "
-                                       "windows), A* query-sharded x%d" % (layout.ti, layout.tj, halo, world))},
-            "roofline": {"bound": "hbm", "kernel": "tsa_search_kernel (astar_search)", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "traffic_provenance": profile_provenance(PMC_SUMMARY),
-                         "algorithmic_bytes_per_launch": alg_bytes, "settled_cells_per_launch": settled_per_launch,
-                         "settled_cells_by_query_set": settled_sets,
-                         "avg_launch_ms": ms_search, "launches": prof["astar_search"][1],
-                         # pipelined launches overlap on the GPU: each one's duration is stretched by the others, so
-                         # the whole-step figure (algorithmic bytes of one launch / wall time of one step) is given too
-                         "overlapped_launches": ms_search / (1e3 * wall_per_pass),
-                         "achieved_per_pass_wall": alg_bytes / wall_per_pass / 1e9,
-                         "frac_wall": alg_bytes / wall_per_pass / 1e9 / HBM_PEAK_GBS,
-                         # the kernel's real bound (not HBM): see valu_issue()
-                         "valu_issue": valu_issue(args, world, wall_per_pass),
-                         "work_inflation": work_inflation(args, world, settled_per_launch, job_counters, passes)},
-            "roofline_rows": [row("himm_raster", HIMM_RASTER_CHAIN, himm_alg),
-                              row("vfh_step", "vfh_step_kernel", float(nq * VFH_BYTES_PER_POSE))],
-            # every kernel slot bracketed by events, in ONE turn of the pipeline run after the timed region (the brackets
-            # slow the engine stream down: these passes are slower than the timed ones)
-            "kernel_ms_per_pass": {k: (v[0] / args.pipeline) for k, v in prof_all.items() if v[1]},
-            "kernel_ms_per_pass_timed_region": {k: (v[0] / passes) for k, v in prof.items() if v[1]},
+                                       "windows), A* query-sharded x%d" % (layout.ti, layout.tj, halo, world)),
+                       "full": args.full},
+            "cpu_baseline": None,
         }
         if layout is not None:
             out["tiled"] = {"layout": [layout.ti, layout.tj], "halo_cells": halo, "windows": windows,
                             "halo_bytes_per_pass_rank0": xfer[0] / passes,
                             "gather_bytes_per_pass_rank0": xfer[1] / passes}
-        if not args.no_cpu and world == 1:   # rank 0 at N=1 only
-            out["cpu_baseline"] = cb = cpu_baseline(args, R, master, ray_sets[0], pose_sets[0], query_sets[0], n, n, length)
-            # the numerator both ways: E of the contract (plateau settled) and of an A* that stops at the goal (sample ratio)
-            ratio = cb["settled_cells_stop_at_goal"] / max(1.0, cb["settled_cells_contract"])
-            out["roofline"]["settled_ratio_stop_at_goal"] = ratio
-            out["roofline"]["frac_wall_stop_at_goal_basis"] = out["roofline"]["frac_wall"] * ratio
-        else:
-            out["cpu_baseline"] = None
+        if outputs is not None:
+            out["config"]["outputs_dumped"] = write_outputs(args.dump_outputs, outputs)
+        if args.full:
+            full_figures(out, args, R, world, passes, wall_per_pass, nq, prof, prof_all, settled_sets, settled_per_launch,
+                         job_counters, ray_sets, master, pose_sets, query_sets, n, length)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     os.close(json_fd)
     e.close()
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_figures(out, args, R, world, passes, wall_per_pass, nq, prof, prof_all, settled_sets, settled_per_launch, job_counters,
+                 ray_sets, master, pose_sets, query_sets, n, length):
+    """--full: the roofline of the search kernel (event brackets of the timed region), the rows of the map update and VFH+ (the
+    profiled turn after it), per-kernel times and the CPU baseline, added to the result line `out`"""
+    import numpy as np
+    ms_search = prof["astar_search"][0] / max(1, prof["astar_search"][1])
+    alg_bytes = settled_per_launch * ASTAR_BYTES_PER_SETTLED
+    achieved = alg_bytes / (ms_search * 1e-3) / 1e9 if ms_search > 0 else 0.0
+    traffic, traffic_src = pmc_traffic("rna::tsa_search_kernel", args, world)
+
+    def row(kernel_key, pmc_name, alg):
+        ms = prof_all[kernel_key][0] / max(1, prof_all[kernel_key][1])
+        gbs = alg / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+        tr, src = pmc_traffic(pmc_name, args, world)
+        return {"kernel": pmc_name if isinstance(pmc_name, str) else " + ".join(pmc_name), "bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
+                "traffic": tr, "traffic_source": src, "algorithmic_bytes_per_launch": alg, "avg_launch_ms": ms,
+                "launches": prof_all[kernel_key][1], "measured": "one turn of the pipeline after the timed region"}
+
+    himm_alg = float(np.mean([(8.0 * np.hypot(r["ex"] - r["sx"], r["ey"] - r["sy"]) / 0.05 + 8.0 * (r["clear_end"] == 0) + 40.0).sum()
+                              for r in ray_sets]))
+    out.update({
+        "roofline": {"bound": "hbm", "kernel": "tsa_search_kernel (astar_search)", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                     "traffic_provenance": profile_provenance(PMC_SUMMARY),
+                     "algorithmic_bytes_per_launch": alg_bytes, "settled_cells_per_launch": settled_per_launch,
+                     "settled_cells_by_query_set": settled_sets,
+                     "avg_launch_ms": ms_search, "launches": prof["astar_search"][1],
+                     # pipelined launches overlap on the GPU: each one's duration is stretched by the others, so
+                     # the whole-step figure (algorithmic bytes of one launch / wall time of one step) is given too
+                     "overlapped_launches": ms_search / (1e3 * wall_per_pass),
+                     "achieved_per_pass_wall": alg_bytes / wall_per_pass / 1e9,
+                     "frac_wall": alg_bytes / wall_per_pass / 1e9 / HBM_PEAK_GBS,
+                     # the kernel's real bound (not HBM): see valu_issue()
+                     "valu_issue": valu_issue(args, world, wall_per_pass),
+                     "work_inflation": work_inflation(args, world, settled_per_launch, job_counters, passes)},
+        "roofline_rows": [row("himm_raster", HIMM_RASTER_CHAIN, himm_alg),
+                          row("vfh_step", "vfh_step_kernel", float(nq * VFH_BYTES_PER_POSE))],
+        # every kernel slot bracketed by events, in ONE turn of the pipeline run after the timed region (the brackets
+        # slow the engine stream down: these passes are slower than the timed ones)
+        "kernel_ms_per_pass": {k: (v[0] / args.pipeline) for k, v in prof_all.items() if v[1]},
+        "kernel_ms_per_pass_timed_region": {k: (v[0] / passes) for k, v in prof.items() if v[1]},
+    })
+    if not args.no_cpu and world == 1:   # rank 0 at N=1 only
+        out["cpu_baseline"] = cb = cpu_baseline(args, R, master, ray_sets[0], pose_sets[0], query_sets[0], n, n, length)
+        # the numerator both ways: E of the contract (plateau settled) and of an A* that stops at the goal (sample ratio)
+        ratio = cb["settled_cells_stop_at_goal"] / max(1.0, cb["settled_cells_contract"])
+        out["roofline"]["settled_ratio_stop_at_goal"] = ratio
+        out["roofline"]["frac_wall_stop_at_goal_basis"] = out["roofline"]["frac_wall"] * ratio
 
 
 if __name__ == "__main__":

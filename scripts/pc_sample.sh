@@ -7,7 +7,7 @@ rm -rf $OUT /tmp/pcs; mkdir -p $OUT /tmp/pcs
 cd /tmp && export TMPDIR=/tmp
 export ROCPROFILER_PC_SAMPLING_BETA_ENABLED=1
 timeout 400 rocprofv3 --pc-sampling-beta-enabled --pc-sampling-unit time --pc-sampling-method host_trap --pc-sampling-interval ${PCS_INTERVAL:-2000} \
-  --kernel-trace --output-format csv -d /tmp/pcs -o pcs -- python3 $ROOT/bench.py --steps 6 --warmup 1 --no-cpu --no-check-paths > $OUT/run.log 2>&1
+  --kernel-trace --output-format csv -d /tmp/pcs -o pcs -- python3 $ROOT/bench.py --full --steps 6 --warmup 1 --no-cpu --no-check-paths > $OUT/run.log 2>&1
 echo "rc $?" >> $OUT/run.log
 find /tmp/pcs -type f | head -20 > $OUT/files.txt
 for f in $(find /tmp/pcs -name "*pc_sampling*csv"); do

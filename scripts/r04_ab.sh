@@ -6,7 +6,7 @@ OUT=gpurun_out/$1; shift
 : > $OUT
 for i in 1 2; do
   for l in "$@"; do
-    env $R04_ENV RNA_LIB=$l timeout 300 python bench.py --no-cpu 2>/tmp/err.txt | python -c "
+    env $R04_ENV RNA_LIB=$l timeout 300 python bench.py --full --no-cpu 2>/tmp/err.txt | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_pass']

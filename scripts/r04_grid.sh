@@ -4,7 +4,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 OUT=gpurun_out/$1; shift
 : > $OUT
 for cfg in "$@"; do
-  env $cfg timeout 300 python bench.py --no-cpu $R04_ARGS 2>/tmp/err.txt | python -c "
+  env $cfg timeout 300 python bench.py --full --no-cpu $R04_ARGS 2>/tmp/err.txt | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_pass']

@@ -6,7 +6,7 @@ OUT=gpurun_out/$1; VAR=$2; shift 2
 : > $OUT
 for i in 1 2; do
   for v in "$@"; do
-    env $VAR=$v timeout 300 python bench.py --no-cpu $R04_ARGS 2>/tmp/err.txt | python -c "
+    env $VAR=$v timeout 300 python bench.py --full --no-cpu $R04_ARGS 2>/tmp/err.txt | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_pass']

@@ -8,7 +8,7 @@ OUT=gpurun_out/r05/$1.txt
 : > $OUT
 run() {   # label, env...
   local label=$1; shift
-  env "$@" timeout 300 python bench.py --no-cpu --steps 20 2>/tmp/err.txt | python -c "
+  env "$@" timeout 300 python bench.py --full --no-cpu --steps 20 2>/tmp/err.txt | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_pass']

@@ -13,7 +13,7 @@ OUT=gpurun_out/r06/${NAME}.txt
 : > $OUT
 for i in $(seq 1 ${R06_ROUNDS:-2}); do
   for l in "$@"; do
-    env $R06_ENV RNA_LIB=$l timeout 300 python bench.py --no-cpu --no-check-paths ${R06_ARGS} 2>/tmp/err.txt | python -c "
+    env $R06_ENV RNA_LIB=$l timeout 300 python bench.py --full --no-cpu --no-check-paths ${R06_ARGS} 2>/tmp/err.txt | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_pass']; w=d['roofline'].get('work_inflation') or {}

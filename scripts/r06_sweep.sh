@@ -9,7 +9,7 @@ OUT=gpurun_out/r06/${NAME}.txt
 for i in 1 2; do
   for v in "$@"; do
     if [[ $VAR == ARG:* ]]; then ENVV=""; ARGS="${VAR#ARG:} $v"; else ENVV="$VAR=$v"; ARGS=""; fi
-    env $ENVV timeout 300 python bench.py --no-cpu --no-check-paths $ARGS 2>/tmp/err.txt | python -c "
+    env $ENVV timeout 300 python bench.py --full --no-cpu --no-check-paths $ARGS 2>/tmp/err.txt | python -c "
 import sys,json
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_pass']

@@ -35,7 +35,7 @@ def test_every_declared_symbol_is_exported(capi):
     assert L.rna_abi_version() == capi.ABI_VERSION == int(re.search(r"#define RNA_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "rna.h")).read()).group(1))
 
 
-def test_struct_layouts_match_header(capi):
+def test_struct_layouts_match_header(capi, tmp_path):
     src = open(os.path.join(ROOT, "include", "rna.h")).read()
     prog = r"""
     #include <stdio.h>
@@ -47,7 +47,7 @@ def test_struct_layouts_match_header(capi):
       printf("%zu %zu %zu %zu\n", sizeof(rna_submap_info), sizeof(rna_range_reading), sizeof(rna_laser_scan_tf), sizeof(rna_range_reading_tf));
       return 0;
     }"""
-    exe = "/tmp/rna_layout_check"
+    exe = str(tmp_path / "rna_layout_check")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=prog.encode(), check=True)
     sizes = [int(x) for x in subprocess.check_output([exe]).split()]
     assert sizes == [C.sizeof(capi.Geometry), capi.RAY_DTYPE.itemsize, C.sizeof(capi.VfhParams),

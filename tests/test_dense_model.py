@@ -15,14 +15,13 @@ import _oracle as O
 from ros_navigation_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SIM = "/tmp/rna_sim_dense2"
-SIM_ASYNC = "/tmp/rna_sim_async"
 
 
 @pytest.fixture(scope="module")
-def sim():
-    subprocess.check_call(["gcc", "-O2", "-o", SIM, os.path.join(ROOT, "scripts", "sim_dense2.c")])
-    return SIM
+def sim(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("sim") / "sim_dense2")
+    subprocess.check_call(["gcc", "-O2", "-o", exe, os.path.join(ROOT, "scripts", "sim_dense2.c")])
+    return exe
 
 
 def workload(path, rows, cols, nq, seed, density, side):
@@ -54,9 +53,10 @@ def test_tile_schedule_model_matches_the_oracle(sim, tmp_path, rows, cols, densi
 
 
 @pytest.fixture(scope="module")
-def sim_async():
-    subprocess.check_call(["gcc", "-O2", "-o", SIM_ASYNC, os.path.join(ROOT, "scripts", "sim_async.c")])
-    return SIM_ASYNC
+def sim_async(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("sim") / "sim_async")
+    subprocess.check_call(["gcc", "-O2", "-o", exe, os.path.join(ROOT, "scripts", "sim_async.c")])
+    return exe
 
 
 @pytest.mark.parametrize("rows,cols,density,side", [(200, 150, 0.30, (2, 20)), (333, 97, 0.45, (1, 6))])

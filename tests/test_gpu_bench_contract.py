@@ -29,7 +29,7 @@ def test_bench_line_contract_on_a_small_grid_through_the_spawn_path_with_rccl():
     from the KFD topology, no torch import) starts the rank with Popen, the rank initialises RCCL (`nccl` backend), runs
     the barriers around the timed region and the max over ranks -- forced at world size 1, un-shared, so that it has run
     on hardware (one subprocess serves both checks: a bench start-up costs a torch import and a map set-up each)."""
-    d = run_bench(["--cpu-seconds", "0.5"], env={"RNA_BENCH_FORCE_SPAWN": "1"})
+    d = run_bench(["--full", "--cpu-seconds", "0.5"], env={"RNA_BENCH_FORCE_SPAWN": "1"})
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "roofline_rows", "cpu_baseline"):
         assert k in d, k
@@ -58,6 +58,40 @@ def test_bench_line_contract_on_a_small_grid_through_the_spawn_path_with_rccl():
     la = cfg["launcher"]
     assert la["spawned_by_bench"] and la["parent_is_my_parent"] and la["parent_hip_free"]
     assert cfg["shards"] == [[0, 32]] and cfg["cycles_by_rank"] == [32 * PASSES]
+
+
+def test_plain_run_times_the_steps_and_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain run (no --full) does the headline only: no roofline, per-kernel times, path check or CPU baseline in its line.
+    --dump-outputs writes what the last timed step computed; two runs with the same arguments write the same arrays."""
+    runs = [run_bench(["--dump-outputs", str(tmp_path / str(i))]) for i in (0, 1)]
+    for d in runs:
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 5 and abs(d["value"] - 32 * PASSES / (d["ms_per_step"] * 5e-3)) < 1e-6 * d["value"]
+        assert d["config"]["full"] is False and d["config"]["paths_checked"] is None and d["cpu_baseline"] is None
+        assert not any(k in d for k in ("roofline", "roofline_rows", "kernel_ms_per_pass", "kernel_ms_per_pass_timed_region"))
+        assert 0 < d["config"]["outputs_dumped"]["bytes"] <= 64 << 20
+    names = sorted(os.listdir(tmp_path / "0"))
+    assert names == sorted(os.listdir(tmp_path / "1")) == sorted(
+        n + ".npy" for n in ("astar_status", "astar_path_len", "astar_cost", "astar_paths_sample", "astar_paths_sample_index",
+                             "vfh_chosen_speed", "vfh_chosen_turnrate", "vfh_picked_angle", "vfh_emergency",
+                             "map_master_sample", "map_laser_sample"))
+    for name in names:
+        a, b = np.load(tmp_path / "0" / name), np.load(tmp_path / "1" / name)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, name
+        assert np.array_equal(a, b, equal_nan=True), name
+    z = {n[:-4]: np.load(tmp_path / "0" / n) for n in names}
+    assert z["astar_status"].shape == (3, 32) and set(np.unique(z["astar_status"]).tolist()) <= {0.0, 1.0}
+    assert z["vfh_chosen_speed"].shape == (32,) and z["map_master_sample"].size == 512 * 512
+    # every sampled path is the one the result record describes: as long as path_len, inside the map, cells of the path
+    found = 0
+    for p, q, off, cells in z["astar_paths_sample_index"].astype(np.int64):
+        ok = z["astar_status"][p, q] == 0
+        assert cells == (z["astar_path_len"][p, q] if ok else 0)
+        path = z["astar_paths_sample"][off:off + cells]
+        assert ((path >= 0) & (path < 512 * 512)).all() and np.array_equal(path, np.round(path))
+        found += ok
+    assert found > 0 and len(z["astar_paths_sample_index"]) == 3 * 32
 
 
 # The 8-GPU bench runs once, unattended, at the end of a round: its two launch modes are rehearsed here at world size 8
@@ -150,10 +184,10 @@ _default_runs = {}
 
 
 def default_bench(cpus=0):
-    """the default bench (full size, 12 steps, --check-paths), run once per setting and shared by the tests below"""
+    """the default bench (full size, 12 steps, --full --check-paths), run once per setting and shared by the tests below"""
     if cpus not in _default_runs:
         env = dict(os.environ, **({"RNA_BENCH_CPUS": str(cpus)} if cpus else {}))
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--no-cpu"] + ([] if cpus else ["--check-paths"]),
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--no-cpu"] + ([] if cpus else ["--check-paths"]),
                              capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
         assert out.returncode == 0, out.stderr[-2000:]
         _default_runs[cpus] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])

@@ -12,7 +12,9 @@ def test_oracle_is_clean_under_asan_ubsan():
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "san"])
     asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
     env = dict(os.environ)
-    env.update(RNA_ORACLE_SO=os.path.join(ROOT, "oracle", "_san", "librna_oracle_san.so"), LD_PRELOAD=asan,
+    # (libasan first, as it must be; whatever the environment preloads already stays preloaded behind it)
+    preload = " ".join(x for x in (asan, os.environ.get("LD_PRELOAD", "")) if x)
+    env.update(RNA_ORACLE_SO=os.path.join(ROOT, "oracle", "_san", "librna_oracle_san.so"), LD_PRELOAD=preload,
                ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     tests = ["test_oracle_gridmap.py", "test_oracle_misc.py", "test_oracle_msgs.py", "test_oracle_scan.py"]
     out = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider"] +
