@@ -2,6 +2,9 @@
  * gridmath.c -- ORACLE (test infrastructure): grid_map_core index/position math, submaps,
  * circular buffer and iterators, restated in plain C.  Compile with -ffp-contract=off so that the
  * double arithmetic is evaluated operation by operation as the reference (x86-64, no FMA) does.
+ * Pinned by the reference's gtest answers (tests/test_oracle_gridmap.py) and bit for bit against the reference's own
+ * grid_map_core (oracle/_ref/libref_gridmap.so): Line / Circle / Submap iterators, getSubmap, move
+ * (tests/test_oracle_refpin.py).
  * gmc/ = /root/reference/grid_map-master/grid_map_core
  */
 #include "rna_oracle.h"
@@ -145,7 +148,12 @@ int og_submap_information(const og_geom* g, const double req_pos[2], const doubl
   sub.res = g->res;
   sub.size[0] = o->size[0]; sub.size[1] = o->size[1];
   sub.start[0] = sub.start[1] = 0;
-  if (!og_index_from_position(&sub, req_pos, o->requested_index)) return 0;
+  /* getIndexFromPosition on the submap (start index 0) checks the bounds only: a requested position within rounding of
+   * the submap's far edge succeeds with index == size.  Nothing reads that index (getSubmap only reports it), so the
+   * far-edge rule of og_index_from_position does not apply here: with it, getSubmap failed where the reference
+   * succeeds (pinned by tests/test_oracle_refpin.py; regression case tests/golden/submap_far_edge_case.npz). */
+  if (!og_position_within_map(req_pos, sub.len, sub.pos)) return 0;
+  for (int a = 0; a < 2; ++a) o->requested_index[a] = -(int)(((req_pos[a] - 0.5 * sub.len[a]) - sub.pos[a]) / sub.res);
   return 1;
 }
 

@@ -1,7 +1,8 @@
 /*
  * himm.c -- ORACLE (test infrastructure): the simplified HIMM cell update of move_control and
- * Steerer::getRangesFromSubmap, restated in plain C.  "parity unpinned": the reference has no
- * test for these and they cannot be built here (ROS/tf/Eigen); reviewed line by line against
+ * Steerer::getRangesFromSubmap, restated in plain C.  og_himm_update is pinned bit for bit against the reference's
+ * own MapUpdater::lineOnMap (oracle/_ref/libref_gridmap.so, tests/test_oracle_refpin.py); getRangesFromSubmap stays
+ * "parity unpinned" beyond its getSubmap (it needs ROS/tf/angles).  Reviewed line by line against
  * mc/include/move_control/map_updater.h:38-71, mc/src/laser_map_updater.cpp:7-21,
  * mc/src/map_provider.cpp:216-223 and mc/src/steerer.cpp:147-191.
  */

@@ -9,12 +9,14 @@
  *
  * Parity pinning status (see DESIGN.md "Oracle"):
  *   - grid index math, submaps, iterators, LineIterator, GridMap::move: pinned by the reference's
- *     own gtest known answers (tests/golden/gridmap_known_answers.json).
+ *     own gtest known answers (tests/test_oracle_gridmap.py) and bit for bit against the reference's own
+ *     grid_map_core compiled into oracle/_ref/libref_gridmap.so (tests/test_oracle_refpin.py).
+ *   - HIMM (og_himm_update) and RRT (og_rrt_plan_steer, steer = 0): pinned against the reference's
+ *     MapUpdater::lineOnMap and RrtPlanner::makePlan in the same library.
  *   - VFH+ (vfh.c): pinned against the reference vfh.cpp compiled here into oracle/_ref and
  *     against committed golden vectors generated from it (tests/golden/vfh_*.json).
- *   - HIMM, getRangesFromSubmap, RRT, graph A*: restated line by line; the reference has no test
- *     or buildable binary for them here -> "parity unpinned" (only RRT's glibc rand() replica is
- *     pinned, against this libc).
+ *   - getRangesFromSubmap, graph A*: restated line by line; the reference has no test or buildable
+ *     binary for them here -> "parity unpinned".
  *   - grid A*: no reference implementation exists (reference A* is a 9-vertex waypoint graph);
  *     the oracle *defines* the contract (DESIGN.md "Grid A* contract").
  */

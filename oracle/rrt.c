@@ -1,8 +1,9 @@
 /*
  * rrt.c -- ORACLE (test infrastructure): goal-biased RRT of move_control restated in plain C.
  * Follows mc/src/rrt_planner.cpp:4-104, mc/include/move_control/rrt_planner.h:17-36 and
- * mc/include/move_control/map_global_planner.h:10-86.  "parity unpinned" except for og_rand(),
- * which replicates glibc's TYPE_3 random()/rand() and is pinned against this libc in the tests.
+ * mc/include/move_control/map_global_planner.h:10-86.  Pinned: steer = 0 against the reference's own
+ * RrtPlanner::makePlan after srand(seed) (oracle/_ref/libref_gridmap.so, tests/test_oracle_refpin.py: status, node
+ * count and every waypoint, bit for bit), and og_rand() against this libc's random()/rand() (glibc TYPE_3).
  *
  * Departures (documented in DESIGN.md):
  *  - rand() is global and unseeded in the reference; every query here owns a generator seeded

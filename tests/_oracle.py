@@ -1,5 +1,5 @@
 """ctypes access to the CPU oracle (oracle/librna_oracle.so) and, when built, to the reference's own
-vfh.cpp (oracle/_ref/libref_vfh.so).  TEST INFRASTRUCTURE ONLY -- the product package never imports
+vfh.cpp (oracle/_ref/libref_vfh.so) and grid_map_core / lineOnMap / RrtPlanner (oracle/_ref/libref_gridmap.so).  TEST INFRASTRUCTURE ONLY -- the product package never imports
 this module.  Built on demand with `make -C oracle`.
 """
 import ctypes as C
@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.environ.get("RNA_ORACLE_SO") or os.path.join(ORACLE_DIR, "librna_oracle.so")   # override: sanitizer build
 REF_SO = os.path.join(ORACLE_DIR, "_ref", "libref_vfh.so")
+REF_GRIDMAP_SO = os.path.join(ORACLE_DIR, "_ref", "libref_gridmap.so")
 
 
 class Geom(C.Structure):
@@ -65,6 +66,7 @@ class RandState(C.Structure):
 Ranges = (C.c_double * 2) * 361
 _lib = None
 _ref = None
+_ref_gridmap = None
 
 
 def build():
@@ -199,6 +201,106 @@ def ref():
         R.refvfh_min_turning_radius.argtypes = [C.c_void_p, C.c_int]
         _ref = R
     return _ref
+
+
+def ref_gridmap():
+    """The reference's own grid_map_core, MapUpdater::lineOnMap and RrtPlanner::makePlan behind
+    oracle/ref_shim/ref_gridmap_shim.cpp (None when oracle/_ref was never built).  Entry points return
+    REF_RANGE_ERROR when the reference indexed a matrix out of range."""
+    global _ref_gridmap
+    if _ref_gridmap is None:
+        if not os.path.exists(REF_GRIDMAP_SO):
+            return None
+        R = C.CDLL(REF_GRIDMAP_SO)
+        d2 = C.POINTER(C.c_double)
+        i2 = C.POINTER(C.c_int)
+        fp = C.POINTER(C.c_float)
+        G = C.POINTER(Geom)
+        R.refgm_index_from_position.argtypes = [G, d2, i2]
+        R.refgm_position_from_index.argtypes = [G, i2, d2]
+        R.refgm_submap_information.argtypes = [G, d2, d2, C.POINTER(SubmapInfo)]
+        R.refgm_line_cells.argtypes = [G, d2, d2, i2, C.c_int]
+        R.refgm_circle_cells.argtypes = [G, d2, C.c_double, i2, C.c_int]
+        R.refgm_submap_cells.argtypes = [G, i2, i2, i2, C.c_int]
+        R.refgm_get_submap.argtypes = [G, fp, d2, d2, G, fp, C.c_int, i2]
+        R.refgm_move.argtypes = [G, C.POINTER(fp), C.c_int, d2, C.POINTER(Region), i2]
+        R.refgm_himm_update.argtypes = [G, fp, C.c_void_p, C.c_int]
+        R.refgm_rrt_plan.argtypes = [G, fp, d2, d2, C.c_double, C.c_uint, C.c_long, d2, C.c_int, C.POINTER(RrtResult)]
+        _ref_gridmap = R
+    return _ref_gridmap
+
+
+REF_RANGE_ERROR = -2
+
+
+def _cells(fn, *args, width=2):
+    cap = 1 << 16
+    out = np.zeros(width * cap, np.int32)
+    n = fn(*args, out.ctypes.data_as(C.POINTER(C.c_int)), cap)
+    assert 0 <= n <= cap, n
+    return out[:width * n].reshape(-1, width).copy()
+
+
+def line_cells(g, s, e, reference=False):
+    """LineIterator(map, s, e) as an (n, 2) index array: the oracle's, or the reference's own"""
+    fn = ref_gridmap().refgm_line_cells if reference else lib().og_line_cells
+    return _cells(fn, C.byref(g), d2(*s), d2(*e))
+
+
+def circle_cells(g, c, r, reference=False):
+    fn = ref_gridmap().refgm_circle_cells if reference else lib().og_circle_cells
+    return _cells(fn, C.byref(g), d2(*c), r)
+
+
+def submap_cells(g, tl, size, reference=False):
+    """SubmapIterator: (n, 4) = buffer index, submap index"""
+    fn = ref_gridmap().refgm_submap_cells if reference else lib().og_submap_cells
+    return _cells(fn, C.byref(g), i2(*tl), i2(*size), width=4)
+
+
+def get_submap(g, layer, pos, length, reference=False):
+    """GridMap::getSubmap of one column-major layer -> (ok, submap og_geom, submap layer)"""
+    sub = Geom()
+    cap = (int(length[0] / g.res) + 3) * (int(length[1] / g.res) + 3)
+    cap = min(cap, g.size[0] * g.size[1])
+    out = np.full(cap, np.nan, np.float32)
+    if reference:
+        req = i2(0, 0)
+        ok = ref_gridmap().refgm_get_submap(C.byref(g), fptr(layer), d2(*pos), d2(*length), C.byref(sub), fptr(out),
+                                            cap, req)
+        assert ok != REF_RANGE_ERROR
+    else:
+        ok = lib().og_get_submap(C.byref(g), fptr(layer), d2(*pos), d2(*length), C.byref(sub), fptr(out), cap)
+    n = sub.size[0] * sub.size[1] if ok == 1 else 0
+    return ok == 1, sub, out[:n].copy()
+
+
+def move(g, layers, new_pos, reference=False):
+    """GridMap::move on column-major layers (in place) and g (in place) -> (regions as tuples, moved)"""
+    ptrs = (C.POINTER(C.c_float) * len(layers))(*[fptr(a) for a in layers])
+    regs = (Region * 4)()
+    moved = C.c_int(0)
+    fn = ref_gridmap().refgm_move if reference else lib().og_move
+    n = fn(C.byref(g), ptrs, len(layers), d2(*new_pos), regs, C.byref(moved))
+    assert 0 <= n <= 4, n
+    return [(tuple(regs[k].index), tuple(regs[k].size), regs[k].quadrant) for k in range(n)], moved.value
+
+
+def ref_himm_update(g, layer, rays):
+    """the reference's MapUpdater::lineOnMap for each ray in order (layer modified in place)"""
+    assert rays.dtype == RAY_DTYPE
+    rc = ref_gridmap().refgm_himm_update(C.byref(g), fptr(layer), rays.ctypes.data, len(rays))
+    assert rc == 0, rc
+
+
+def ref_rrt_plan(g, master, start, target, tol=0.2, seed=1, max_rand=600000, cap=2048):
+    """srand(seed) then the reference's RrtPlanner::makePlan; status -1 when it used more than max_rand rand() calls"""
+    path = np.zeros(2 * cap, np.float64)
+    res = RrtResult()
+    rc = ref_gridmap().refgm_rrt_plan(C.byref(g), fptr(master), d2(*start), d2(*target), tol, seed, max_rand,
+                                      path.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(res))
+    assert rc == 0, rc
+    return res, path[:2 * min(res.path_len, cap)].reshape(-1, 2).copy()
 
 
 # ---------------------------------------------------------------------------------------------
