@@ -32,7 +32,9 @@ extern "C" {
  * 4: rna_scan_to_rays_tf[_device], rna_range_to_rays_tf (sensors with a full tf transform; round 4); no existing signature changed.
  * 5: rna_astar_job_counters (round 6); the default bucket width of the grid search is 128000, a pipeline may have up to 20 stages,
  *    rna_astar_result.rounds counts every job again (also the ones that find nothing); no existing signature changed. */
-#define RNA_ABI_VERSION 5
+/* 6: robot radius of the grid A* (rna_astar_set_robot_radius / _get_robot_radius, rna_astar_download_blocked),
+ *    rna_if_blocked_batch[_device], profile slot footprint; no existing signature changed. */
+#define RNA_ABI_VERSION 6
 
 typedef enum {
   RNA_OK = 0,
@@ -310,6 +312,28 @@ int rna_astar_settled_counts(rna_engine* e, int32_t* counts_host, int n);
 int rna_astar_job_counters(rna_engine* e, uint64_t* counters_host, int reset);
 /* per-cell traversable-neighbour mask derived from the master layer (rows*cols uint8) */
 int rna_astar_download_nbr_mask(rna_engine* e, uint8_t* host, size_t n_cells);
+/* Robot radius r (metres) of the grid A*: the footprint GlobalPlanner::ifBlocked checks with its 0.3 m disc
+ * (mc/include/move_control/map_global_planner.h:39-54, "the radius should be configured from ROS::Parameter footPrint").
+ * r == 0 (the default): a cell is blocked iff its own master value is finite and > 0, as before.  r > 0: a cell c is
+ * blocked iff ifBlocked(getPosition(c)) with radius r is true -- some cell that CircleIterator(map, centre of c, r)
+ * visits (gmc/src/iterators/CircleIterator.cpp:16-93) holds a finite master value > 0; NaN does not block, cells
+ * outside the map are not visited.  The neighbour masks, costs and statuses follow from that blocked set by the rules
+ * of DESIGN.md's grid A* contract; a start or goal in the inflated region answers as a blocked one.  Valid:
+ * 0 <= r and r / resolution <= 63, anything else is RNA_EINVAL.  Batches already issued keep the masks they were
+ * issued with; the next batch (or rna_astar_download_nbr_mask) sees the new radius.  rna_clone and rna_create_submap
+ * copy it. */
+int rna_astar_set_robot_radius(rna_engine* e, double radius);
+int rna_astar_get_robot_radius(const rna_engine* e, double* radius);
+/* the blocked set the search uses (rows*cols uint8 in buffer order, 1 = blocked), refreshed first as
+ * rna_astar_download_nbr_mask is: with r == 0 the master layer's finite-and-> 0 cells */
+int rna_astar_download_blocked(rna_engine* e, uint8_t* host, size_t n_cells);
+/* GlobalPlanner::ifBlocked (map_global_planner.h:39-54, CircleIterator.cpp:16-93) at n arbitrary positions (xy: n x 2
+ * doubles) with a chosen radius (finite, >= 0; the reference's is 0.3) on the master layer: out[k] = 1 blocked, 0 free.
+ * A check of a tailored or followed plan (mc/src/nav_node.cpp:192-204) or of poses from a caller's own sampler.
+ * Corners of the disc's bounding box within rounding of the map's far edge are handled as oracle/gridmath.c
+ * og_circle_cells and oracle/rrt.c og_if_blocked define them.  The _device form is asynchronous on the engine stream. */
+int rna_if_blocked_batch(rna_engine* e, const double* xy_host, int n, double radius, uint8_t* out_host);
+int rna_if_blocked_batch_device(rna_engine* e, const double* xy_device, int n, double radius, uint8_t* out_device);
 
 /* ---- global planning: waypoint-graph A* (the reference's own AStarPlanner) ------------------- */
 /* AStarPlanner::init + makePlan over a caller-supplied graph (astar_planner.cpp:63-145): start and
@@ -428,7 +452,8 @@ int rna_follow_plan(const double* plan_xy, int n, int32_t* plan_index, double x,
 /* ---- measurement ------------------------------------------------------------------------------ */
 typedef enum {
   RNA_K_HIMM_PREP = 0, RNA_K_HIMM_RASTER, RNA_K_HIMM_APPLY, RNA_K_COMPOSE, RNA_K_NBRMASK,
-  RNA_K_VFH_STEP, RNA_K_ASTAR_SEARCH, RNA_K_ASTAR_INIT, RNA_K_RRT, RNA_K_OCCUPANCY, RNA_K_ASTAR_RESET, RNA_K_COUNT
+  RNA_K_VFH_STEP, RNA_K_ASTAR_SEARCH, RNA_K_ASTAR_INIT, RNA_K_RRT, RNA_K_OCCUPANCY, RNA_K_ASTAR_RESET,
+  RNA_K_FOOTPRINT, RNA_K_COUNT
 } rna_kernel_id;
 /* when enabled, every launch of the kernels above is bracketed by hipEvents on the stream it runs on (the engine
  * stream; astar_search: the pipeline stage's own stream; astar_init / astar_reset / vfh_step: the side stream) */

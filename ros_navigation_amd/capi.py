@@ -14,12 +14,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("RNA_LIB") or "librna.so")   # RNA_LIB: developer switch to an alternative build
 
 RNA_OK = 0
-ABI_VERSION = 5   # include/rna.h: RNA_ABI_VERSION
+ABI_VERSION = 6   # include/rna.h: RNA_ABI_VERSION
 STATUS = {0: "RNA_OK", -1: "RNA_EINVAL", -2: "RNA_ENOMEM", -3: "RNA_EHIP", -4: "RNA_ECAPACITY",
           -5: "RNA_ESTATE", -6: "RNA_ENODEVICE"}
 LAYER_MASTER, LAYER_LASER, LAYER_RANGE = 0, 1, 2
 KERNELS = ["himm_prep", "himm_raster", "himm_apply", "compose_master", "nbr_mask", "vfh_step",
-           "astar_search", "astar_init", "rrt", "to_occupancy_grid", "astar_reset"]
+           "astar_search", "astar_init", "rrt", "to_occupancy_grid", "astar_reset", "footprint"]
 
 # every symbol include/rna.h declares (tests/test_capi_symbols.py checks the header against this)
 SYMBOLS = [
@@ -34,7 +34,8 @@ SYMBOLS = [
     "rna_vfh_default_params", "rna_vfh_init", "rna_vfh_reset", "rna_vfh_hist_size", "rna_vfh_step_batch",
     "rna_vfh_step_batch_device", "rna_vfh_update_batch",
     "rna_astar_configure", "rna_astar_set_pipeline_depth", "rna_astar_set_page_cap", "rna_astar_effective_config", "rna_astar_batch", "rna_astar_batch_device", "rna_astar_settled_counts", "rna_astar_job_counters",
-    "rna_astar_download_nbr_mask",
+    "rna_astar_download_nbr_mask", "rna_astar_set_robot_radius", "rna_astar_get_robot_radius", "rna_astar_download_blocked",
+    "rna_if_blocked_batch", "rna_if_blocked_batch_device",
     "rna_graph_astar_batch", "rna_rrt_batch", "rna_rrt_batch_device",
     "rna_to_occupancy_grid", "rna_to_occupancy_grid_device", "rna_from_occupancy_grid", "rna_vfh_hist_msg_batch",
     "rna_tailor_plan", "rna_follow_plan", "rna_get_submap", "rna_get_submap_device", "rna_create_submap", "rna_scan_to_rays", "rna_scan_to_rays_device", "rna_scan_projected_beams", "rna_range_to_rays",
@@ -176,6 +177,11 @@ def lib():
     L.rna_astar_batch.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     L.rna_astar_batch_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     L.rna_astar_download_nbr_mask.argtypes = [vp, vp, C.c_size_t]
+    L.rna_astar_set_robot_radius.argtypes = [vp, C.c_double]
+    L.rna_astar_get_robot_radius.argtypes = [vp, C.POINTER(C.c_double)]
+    L.rna_astar_download_blocked.argtypes = [vp, vp, C.c_size_t]
+    L.rna_if_blocked_batch.argtypes = [vp, vp, C.c_int, C.c_double, vp]
+    L.rna_if_blocked_batch_device.argtypes = [vp, vp, C.c_int, C.c_double, vp]
     L.rna_astar_settled_counts.argtypes = [vp, vp, C.c_int]
     if hasattr(L, "rna_astar_job_counters"):   # (absent only in an older build named by the developer switch RNA_LIB of bench.py's A/B runs)
         L.rna_astar_job_counters.argtypes = [vp, vp, C.c_int]
@@ -602,6 +608,31 @@ class Engine:
         a = np.empty(self.ncell, np.uint8)
         self._check(self._L.rna_astar_download_nbr_mask(self.h, _ptr(a), a.size))
         return a
+
+    def astar_robot_radius(self, r=None):
+        """Robot radius of the grid A* in metres (rna_astar_set_robot_radius): sets it when r is given, returns it.
+        0 = point robot; r > 0 blocks every cell whose GlobalPlanner::ifBlocked disc of radius r holds an obstacle."""
+        if r is not None:
+            self._check(self._L.rna_astar_set_robot_radius(self.h, float(r)))
+        out = C.c_double(0.0)
+        self._check(self._L.rna_astar_get_robot_radius(self.h, C.byref(out)))
+        return out.value
+
+    def astar_blocked_mask(self):
+        """the blocked set the grid A* searches with (buffer order, 1 = blocked)"""
+        a = np.empty(self.ncell, np.uint8)
+        self._check(self._L.rna_astar_download_blocked(self.h, _ptr(a), a.size))
+        return a
+
+    def if_blocked(self, xy, radius):
+        """GlobalPlanner::ifBlocked with `radius` at every position of xy (n x 2): uint8, 1 = blocked"""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        out = np.zeros(len(xy), np.uint8)
+        self._check(self._L.rna_if_blocked_batch(self.h, _ptr(xy), len(xy), float(radius), _ptr(out)))
+        return out
+
+    def if_blocked_device(self, xy_ptr, n, radius, out_ptr):
+        self._check(self._L.rna_if_blocked_batch_device(self.h, xy_ptr, n, float(radius), out_ptr))
 
     def graph_astar(self, vertex_xy, edge_uv, start_target, edge_weight=None, max_len=None):
         v = np.ascontiguousarray(vertex_xy, dtype=np.float64).reshape(-1, 2)

@@ -223,7 +223,8 @@ extern "C" const char* rna_last_error(const rna_engine* e) { return e ? e->err.c
 
 extern "C" const char* rna_kernel_name(int id) {
   static const char* names[RNA_K_COUNT] = {"himm_prep", "himm_raster", "himm_apply", "compose_master", "nbr_mask",
-                                           "vfh_step", "astar_search", "astar_init", "rrt", "to_occupancy_grid", "astar_reset"};
+                                           "vfh_step", "astar_search", "astar_init", "rrt", "to_occupancy_grid", "astar_reset",
+                                           "footprint"};
   return (id >= 0 && id < RNA_K_COUNT) ? names[id] : "?";
 }
 
@@ -294,6 +295,7 @@ extern "C" void rna_destroy(rna_engine* e) {
   himm_release(e);
   vfh_release(e);
   astar_release(e);
+  footprint_release(e);
   for (int l = 0; l < RNA_NUM_LAYERS; ++l) dev_free(&e->layer[l]);
   dev_free(&e->dirty_tiles);
   dev_free(&e->last_dirty);
@@ -564,6 +566,7 @@ extern "C" int rna_create_submap(rna_engine* parent, double px, double py, doubl
   }
   c->nbr_all_dirty = true;
   c->laser_all_dirty = true;
+  c->robot_r = parent->robot_r;
   *out = c;
   return 1;
 }
@@ -592,6 +595,7 @@ extern "C" int rna_clone(rna_engine* src, rna_engine** out) {
   }
   c->nbr_all_dirty = true;
   c->laser_all_dirty = true;
+  c->robot_r = src->robot_r;
   *out = c;
   return RNA_OK;
 }
@@ -765,6 +769,12 @@ int profile_flush(rna_engine* e) {
 int map_prepare_nbr(rna_engine* e) {
   if (!e->nbr_all_dirty) return RNA_OK;
   { const int rc = side_join(e); if (rc != RNA_OK) return rc; }   // snapshots in flight read the masks this rebuilds
+  if (e->robot_r > 0.0) {   // robot radius: the blocked set of the disc (footprint.hip)
+    const int rc = footprint_refresh(e, 1);
+    if (rc != RNA_OK) return rc;
+    e->nbr_all_dirty = false;
+    return RNA_OK;
+  }
   KernelTimer kt(e, RNA_K_NBRMASK);
   hipLaunchKernelGGL(nbr_mask_tiles_kernel, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream, e->nbr,
                      e->layer[RNA_LAYER_MASTER], e->dirty_tiles, 1, e->geom.size[0], e->geom.size[1], e->tiles_i,
@@ -782,7 +792,7 @@ extern "C" int rna_compose_master(rna_engine* e, int mode) {
   const size_t words = ((size_t)e->tiles_i * e->tiles_j + 3) / 4;  // one byte per tile, rounded to words
   const bool full = (mode == 1) || e->laser_all_dirty || e->master_diverged;
   const bool moved = e->geom.start[0] != 0 || e->geom.start[1] != 0;
-  if (!full && !moved && !e->nbr_all_dirty) {
+  if (!full && !moved && !e->nbr_all_dirty && e->robot_r == 0.0) {
     // the usual case of the replan loop: dirty tiles only, masks valid before -- one launch, and the two flag arrays
     // swap roles (what this compose consumed = rna_last_dirty_tiles; the other one, cleared by the launch, is marked next)
     KernelTimer kt(e, RNA_K_COMPOSE);
@@ -810,6 +820,10 @@ extern "C" int rna_compose_master(rna_engine* e, int mode) {
     // a layer was replaced wholesale: nothing is known about which masks are still valid; moved map: dirty tiles (buffer
     // space) do not line up with mask tiles (map space) -- the masks are rebuilt before the next search (map_prepare_nbr)
     e->nbr_all_dirty = true;
+  } else if (!e->nbr_all_dirty && e->robot_r > 0.0) {
+    // robot radius: the same tiles (a changed tile reaches r / res <= 63 cells, inside its ring) through footprint.hip
+    const int rc = footprint_refresh(e, 0);
+    if (rc != RNA_OK) return rc;
   } else if (!e->nbr_all_dirty) {
     // masks were valid before this update: refresh only tiles that are dirty or touch a dirty tile
     KernelTimer kt(e, RNA_K_NBRMASK);

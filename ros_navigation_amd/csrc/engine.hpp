@@ -122,6 +122,19 @@ struct AstarDevice {
   int last_n = 0;
 };
 
+// The disc of GlobalPlanner::ifBlocked with radius r as a stencil of cell offsets (footprint.hip): every offset (di, dj),
+// |di|, |dj| <= R = ceil(r / res), is sure-in, sure-out or a tie by the nominal distance (di^2 + dj^2) res^2 against r^2
+// with a margin that bounds the rounding of the reference's f64 cell-centre arithmetic for coordinates up to `mag`.
+// Row dj's sure-in offsets are di in [-w[|dj|], w[|dj|]] (w = -1: none); ties are evaluated per cell in f64.
+struct FootprintPlan {
+  double r = 0.0, res = 0.0, mag = 0.0;   // radius, resolution and coordinate magnitude the plan was made for
+  int R = 0;                              // stencil half-extent (cells)
+  int K = 0;                              // largest |di| (= |dj|) of an offset that is not sure-out (<= R)
+  int band = 0;                           // cells closer than this to the map edge (map space) check their bounding box
+  int n_ties = 0;
+  int w[64] = {};
+};
+
 struct ProfSlot {
   double total_ms = 0;
   int64_t launches = 0;
@@ -152,6 +165,14 @@ struct rna_engine {
   bool master_diverged = false;      // master written directly: next compose is a whole-layer copy
   uint8_t* nbr = nullptr;            // A* neighbour masks derived from master
   bool nbr_all_dirty = true;
+  // Robot radius of the grid A* (rna_astar_set_robot_radius, footprint.hip): 0 = point robot (the masks come from
+  // nbr_mask_tiles_kernel / compose_nbr_tiles_kernel exactly as before); > 0 = the masks are built from the blocked set
+  // of GlobalPlanner::ifBlocked with this radius by footprint_tiles_kernel.
+  double robot_r = 0.0;
+  unsigned long long* fp_bits = nullptr;       // r > 0: blocked set, 64 x 64 bits per MAP-space tile (word = row j, bit = i)
+  rna::FootprintPlan fp{};           // r > 0: the disc stencil, classified for the geometry's coordinate magnitude
+  int2* fp_ties = nullptr;           // r > 0: the tie offsets of fp (device)
+  int fp_ties_cap = 0;
   rna::HimmScratch himm;
   rna::VfhDevice vfh;
   rna::AstarDevice astar;
@@ -245,6 +266,10 @@ int himm_release(rna_engine* e);
 int vfh_release(rna_engine* e);
 int astar_release(rna_engine* e);
 int map_prepare_nbr(rna_engine* e);   // make e->nbr consistent with the master layer
+// robot radius > 0 (footprint.hip): blocked set + neighbour masks of every tile (all != 0) or of the tiles that are dirty
+// or touch a dirty tile (unmoved map), on the engine stream -- the r > 0 replacement of nbr_mask_tiles_kernel
+int footprint_refresh(rna_engine* e, int all);
+int footprint_release(rna_engine* e);
 int sync_all(rna_engine* e);          // main stream + every A* side stream
 // tile-synchronous A* (astar_tile.hip)
 bool tsa_supported(const rna_engine* e);

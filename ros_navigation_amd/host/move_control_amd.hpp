@@ -548,13 +548,26 @@ class AStarPlanner {
 };
 
 // Grid A* over the GridMap's master layer (BASELINE.json's planner): same makePlan shape.
+static_assert(RNA_ABI_VERSION >= 6, "GridAStarPlanner's robot radius needs include/rna.h ABI version 6");
 class GridAStarPlanner {
  public:
   // One synchronous query at a time is the reference's usage (nav_graph_node.cpp): one search field, no
   // pipelining -- 4 B per cell of HBM instead of the batch default (256 fields x 4 stages).
-  explicit GridAStarPlanner(GridMap& map, int concurrent_queries = 1) : map_(map) {
+  // robot_radius (metres): the disc GlobalPlanner::ifBlocked checks (map_global_planner.h:39-54, 0.3 m there); 0 = a
+  // point robot.  It is a setting of the map's engine (rna_astar_set_robot_radius): every planner on that map shares it.
+  explicit GridAStarPlanner(GridMap& map, int concurrent_queries = 1, double robot_radius = 0.0) : map_(map) {
     grid_map::rna_check(rna_astar_set_pipeline_depth(map.engine(), 1), map.engine(), "GridAStarPlanner");
     grid_map::rna_check(rna_astar_configure(map.engine(), concurrent_queries, 0, 0), map.engine(), "GridAStarPlanner");
+    if (robot_radius != 0.0) setRobotRadius(robot_radius);
+  }
+  // 0 <= radius, radius / resolution <= 63 (std::runtime_error otherwise); the next makePlan plans with it
+  void setRobotRadius(double radius) {
+    grid_map::rna_check(rna_astar_set_robot_radius(map_.engine(), radius), map_.engine(), "GridAStarPlanner::setRobotRadius");
+  }
+  double getRobotRadius() const {
+    double r = 0.0;
+    grid_map::rna_check(rna_astar_get_robot_radius(map_.engine(), &r), map_.engine(), "GridAStarPlanner::getRobotRadius");
+    return r;
   }
   bool makePlan(Position& start, Position& target, std::vector<Position>& path) {
     grid_map::Index s, t;

@@ -1,0 +1,366 @@
+"""GPU: the grid A* planning for a robot of radius r (rna_astar_set_robot_radius, csrc/footprint.hip) against the
+reference's own GlobalPlanner::ifBlocked predicate.  The inflated reference: cell c is blocked iff some cell that the
+reference's compiled CircleIterator (oracle/_ref/libref_gridmap.so; the pinned restatement og_circle_cells where that
+library was not built) visits around getPosition(c) with radius r holds a master value that is not NaN and > 0.  The
+A* reference is og_astar_query_on_map on a stand-in master holding 1.0 where that set is blocked and 0.0 elsewhere."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import _oracle as O
+
+pytestmark = pytest.mark.gpu
+
+REFERENCE = O.ref_gridmap() is not None
+_discs = {}
+
+
+@pytest.fixture(scope="module")
+def R():
+    import ros_navigation_amd as R
+    R.capi.lib()
+    return R
+
+
+def geom_key(g):
+    return (tuple(g.len), tuple(g.pos), g.res, tuple(g.size), tuple(g.start))
+
+
+def centre(g, bi, bj):
+    p = O.d2(0.0, 0.0)
+    O.lib().og_position_from_index(C.byref(g), O.i2(bi, bj), p)
+    return p[0], p[1]
+
+
+def disc_lists(g, r):
+    """per buffer cell, the in-map buffer cells CircleIterator(map, centre, r) visits: (offsets, linear indices)"""
+    key = (geom_key(g), r)
+    if key not in _discs:
+        rows, cols = g.size[0], g.size[1]
+        offs, idx = [0], []
+        for lin in range(rows * cols):
+            c = O.circle_cells(g, centre(g, lin % rows, lin // rows), r, reference=REFERENCE)
+            ok = (c[:, 0] >= 0) & (c[:, 0] < rows) & (c[:, 1] >= 0) & (c[:, 1] < cols)
+            idx.append(c[ok, 0] + c[ok, 1] * rows)
+            offs.append(offs[-1] + int(ok.sum()))
+        _discs[key] = (np.array(offs), np.concatenate(idx).astype(np.int64))
+    return _discs[key]
+
+
+def ref_blocked(g, master, r):
+    occ = (~np.isnan(master)) & (master > 0)
+    offs, idx = disc_lists(g, r)
+    hit = np.concatenate([[0], np.cumsum(occ[idx])])
+    return (hit[offs[1:]] - hit[offs[:-1]] > 0).astype(np.uint8)
+
+
+def map_nbr(g, blocked):
+    """og_astar_nbr_mask of a blocked set, taken in MAP space (a moved map's neighbours wrap round the buffer, not the edge)"""
+    rows, cols, s0, s1 = g.size[0], g.size[1], g.start[0], g.start[1]
+    b = np.roll(np.roll(blocked.reshape(cols, rows), -s1, axis=0), -s0, axis=1)
+    nbr = np.zeros(rows * cols, np.uint8)
+    u8 = C.POINTER(C.c_uint8)
+    b = np.ascontiguousarray(b.reshape(-1))
+    O.lib().og_astar_nbr_mask(b.ctypes.data_as(u8), rows, cols, nbr.ctypes.data_as(u8))
+    return np.roll(np.roll(nbr.reshape(cols, rows), s1, axis=0), s0, axis=1).reshape(-1)
+
+
+def sample_map(rows, cols, seed, occupied=0.004, edge=True):
+    """sparse obstacles (single cells and small blocks), unknown (NaN) cells, and obstacles on every map edge"""
+    rng = np.random.default_rng(seed)
+    m = np.zeros((cols, rows), np.float32)
+    m[rng.random((cols, rows)) < occupied] = 100.0
+    for _ in range(3):
+        i, j = rng.integers(0, rows - 4), rng.integers(0, cols - 4)
+        m[j:j + 3, i:i + 4] = 180.0
+    m[rng.random((cols, rows)) < 0.08] = np.nan
+    if edge:
+        m[0, rng.integers(0, rows)] = 50.0
+        m[-1, rng.integers(0, rows)] = 50.0
+        m[rng.integers(0, cols), 0] = 50.0
+        m[rng.integers(0, cols), -1] = 50.0
+        m[-1, -1] = 7.0
+    return m.reshape(-1)
+
+
+def make(R, rows, cols, pos, master, res=0.05):
+    e = R.Engine(rows * res, cols * res, res, *pos)
+    g = O.make_geom(rows * res, cols * res, res, *pos)
+    assert (e.rows, e.cols) == (rows, cols) == (g.size[0], g.size[1])
+    e.upload(R.capi.LAYER_MASTER, master)
+    return e, g
+
+
+def move_both(R, e, g, master, target):
+    ref = master.copy()
+    ptrs = (C.POINTER(C.c_float) * 1)(O.fptr(ref))
+    regs = (O.Region * 4)()
+    mv = C.c_int(0)
+    O.lib().og_move(C.byref(g), ptrs, 1, O.d2(*target), regs, C.byref(mv))
+    assert e.move(*target) and tuple(e.geometry().start_index) == tuple(g.start) != (0, 0)
+    return ref
+
+
+def check_masks(e, g, master, r):
+    want = ref_blocked(g, master, r)
+    got = e.astar_blocked_mask()
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, ("r=%g" % r, bad[:10], got[bad[:10]], want[bad[:10]])
+    assert np.array_equal(e.nbr_mask(), map_nbr(g, want)), "r=%g" % r
+    return want
+
+
+CASES = [  # rows, cols, position, radii
+    (96, 80, (1.25, -2.5), (0.05, 0.1, 0.25, 0.3, 0.33, 63 * 0.05)),
+    (257, 131, (1000.3, -517.9), (0.05, 0.25, 0.3, 0.33)),
+    (257, 131, (1.25, -2.5), (0.1,)),
+    (96, 80, (1000.3, -517.9), (0.3, 63 * 0.05)),
+]
+
+
+@pytest.mark.parametrize("rows,cols,pos,radii", CASES)
+def test_blocked_set_matches_reference_predicate(R, rows, cols, pos, radii):
+    master = sample_map(rows, cols, seed=rows + cols)
+    e, g = make(R, rows, cols, pos, master)
+    for r in radii:
+        assert e.astar_robot_radius(r) == r
+        check_masks(e, g, master, r)
+    e.close()
+
+
+def test_blocked_set_on_a_moved_map(R):
+    rows, cols = 96, 80
+    master = sample_map(rows, cols, seed=5)
+    e, g = make(R, rows, cols, (1.25, -2.5), master)
+    e.astar_robot_radius(0.3)
+    check_masks(e, g, master, 0.3)
+    ref = move_both(R, e, g, master, (2.33, -1.61))
+    for r in (0.3, 0.25, 63 * 0.05):
+        e.astar_robot_radius(r)
+        check_masks(e, g, ref, r)
+    e.close()
+
+
+def check_search(e, g, blocked, q, res, paths, settled, moved):
+    stand_in = blocked.astype(np.float32)
+    found = 0
+    for k in range(len(q)):
+        ores, opath = O.astar_query_on_map(g, stand_in, q["start"][k], q["goal"][k])
+        if moved:
+            assert res["status"][k] == (0 if ores.status == 0 else 1), k
+        else:
+            assert res["status"][k] == ores.status, k
+        if ores.status == 0:
+            assert res["path_len"][k] == ores.path_len and res["cost"][k] == ores.cost, k
+            assert np.array_equal(paths[k][:ores.path_len], opath), k
+            if settled is not None:
+                assert settled[k] == ores.settled, k
+            found += 1
+    return found
+
+
+def queries(rng, blocked, n, want_band):
+    """random free cells plus starts / goals inside the inflated band (blocked for the robot, free for a point)"""
+    free = np.flatnonzero(blocked == 0)
+    q = np.zeros(n, np.dtype([("start", "<i4"), ("goal", "<i4")]))
+    q["start"], q["goal"] = rng.choice(free, n), rng.choice(free, n)
+    band = np.flatnonzero(want_band)
+    if band.size:
+        q["start"][:8] = rng.choice(band, 8)
+        q["goal"][8:16] = rng.choice(band, 8)
+    q["goal"][16] = q["start"][16]
+    return q
+
+
+@pytest.mark.parametrize("rows,cols,pos,r,moved", [(96, 80, (1.25, -2.5), 0.3, False), (257, 131, (1000.3, -517.9), 0.25, False),
+                                                   (257, 131, (1.25, -2.5), 0.3, True)])
+def test_search_matches_oracle(R, rows, cols, pos, r, moved):
+    master = sample_map(rows, cols, seed=7 + rows, occupied=0.002)
+    e, g = make(R, rows, cols, pos, master)
+    if moved:
+        master = move_both(R, e, g, master, (pos[0] + 3.37, pos[1] - 1.12))
+    e.astar_robot_radius(r)
+    e.astar_configure(max_queries=96)
+    blocked = check_masks(e, g, master, r)
+    point = (~np.isnan(master)) & (master > 0)
+    q = queries(np.random.default_rng(rows), blocked, 96, (blocked == 1) & ~point)
+    res, paths = e.astar(q, 8192)
+    settled = e.astar_settled(len(q))
+    found = check_search(e, g, blocked, q, res, paths, settled, moved)
+    assert found >= 32
+    assert (res["status"][:16] != 0).all()          # a start or goal inside the inflated band answers as a blocked one
+    e.close()
+
+
+class _Hip:
+    def __init__(self):
+        self.h = C.CDLL("libamdhip64.so")
+        self.h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        self.h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        self.h.hipFree.argtypes = [C.c_void_p]
+
+    def alloc(self, nbytes):
+        p = C.c_void_p()
+        assert self.h.hipMalloc(C.byref(p), nbytes) == 0
+        return p.value
+
+    def upload(self, a):
+        a = np.ascontiguousarray(a)
+        p = self.alloc(a.nbytes)
+        assert self.h.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0
+        return p
+
+    def download(self, p, dtype, count):
+        out = np.empty(count, dtype)
+        assert self.h.hipMemcpy(out.ctypes.data, p, out.nbytes, 2) == 0
+        return out
+
+
+def rays(rng, n, half, cx=0.0, cy=0.0, hit=0.7):
+    r = np.zeros(n, O.RAY_DTYPE)
+    ox, oy = rng.uniform(-half, half, n) + cx, rng.uniform(-half, half, n) + cy
+    th, ln = rng.uniform(-np.pi, np.pi, n), rng.uniform(0.0, half, n)
+    r["sx"], r["sy"] = ox, oy
+    r["ex"], r["ey"] = ox + ln * np.cos(th), oy + ln * np.sin(th)
+    r["clear_end"] = (rng.random(n) >= hit).astype(np.int32)
+    return r
+
+
+def test_pipelined_batches_keep_their_snapshot_across_updates_and_radius_changes(R):
+    """depth-4 pipeline, rna_update_map (compose mode 0: the incremental refresh) between batches and a radius change
+    after the fourth: every batch answers for the map AND the radius of its launch.  (Few marking rays and a second radius
+    of 0.25 m keep the free space connected: 44-64 of the 64 queries of each batch have a path, and 39-60 of them answer
+    differently under the other radius.)"""
+    hip = _Hip()
+    rows = cols = 128
+    master = sample_map(rows, cols, seed=11, occupied=0.002, edge=False)
+    e, g = make(R, rows, cols, (0.0, 0.0), master)
+    e.upload(R.capi.LAYER_LASER, master)
+    e.compose_master(1)
+    e.astar_robot_radius(0.15)
+    e.astar_pipeline_depth(4)
+    e.astar_configure(max_queries=64)
+    rng = np.random.default_rng(2)
+    ref, nq, max_len = master.copy(), 64, 4096
+    issued = []
+    for b in range(6):
+        rs = rays(rng, 200, 2.5, hit=0.15)
+        O.himm_update(g, ref, rs)
+        e.update_map(rs.view(R.capi.RAY_DTYPE), compose_mode=0)
+        if b == 3:
+            e.astar_robot_radius(0.25)
+        r = e.astar_robot_radius()
+        blocked = ref_blocked(g, ref, r)
+        q = queries(rng, blocked, nq, np.zeros(0))
+        d_q, d_paths, d_res = hip.upload(q), hip.alloc(nq * max_len * 4), hip.alloc(nq * 24)
+        e.astar_device(d_q, nq, d_paths, max_len, d_res)
+        issued.append((blocked, q, d_q, d_paths, d_res))
+    e.synchronize()
+    for blocked, q, d_q, d_paths, d_res in issued:
+        res = hip.download(d_res, R.capi.ASTAR_RESULT_DTYPE, nq)
+        paths = hip.download(d_paths, np.int32, nq * max_len).reshape(nq, max_len)
+        assert check_search(e, g, blocked, q, res, paths, None, False) >= nq // 4
+        for p in (d_q, d_paths, d_res):
+            hip.h.hipFree(p)
+    assert np.array_equal(e.astar_blocked_mask(), ref_blocked(g, ref, 0.25))
+    e.close()
+
+
+def test_incremental_refresh_equals_full_rebuild(R):
+    rows, cols = 200, 150
+    master = sample_map(rows, cols, seed=3, occupied=0.002)
+    e, g = make(R, rows, cols, (0.4, -0.3), master)
+    e.upload(R.capi.LAYER_LASER, master)
+    e.compose_master(1)
+    e.astar_robot_radius(0.3)
+    e.nbr_mask()                                      # the full build; the updates below refresh dirty tiles + ring
+    rng = np.random.default_rng(9)
+    ref = master.copy()
+    for _ in range(4):
+        rs = rays(rng, 400, 4.0, 0.4, -0.3)
+        O.himm_update(g, ref, rs)
+        e.update_map(rs.view(R.capi.RAY_DTYPE), compose_mode=0)
+    inc_blocked, inc_nbr = e.astar_blocked_mask(), e.nbr_mask()
+    e.astar_robot_radius(0.3)                         # the same radius again: a full rebuild of the same master
+    assert np.array_equal(inc_blocked, e.astar_blocked_mask())
+    assert np.array_equal(inc_nbr, e.nbr_mask())
+    assert np.array_equal(inc_blocked, ref_blocked(g, ref, 0.3))
+    e.close()
+
+
+def test_if_blocked_matches_reference_predicate(R):
+    rows, cols, pos, res = 96, 80, (1.25, -2.5), 0.05
+    master = sample_map(rows, cols, seed=21)
+    e, g = make(R, rows, cols, pos, master)
+    occ = (~np.isnan(master)) & (master > 0)
+    rng = np.random.default_rng(4)
+    L = np.array([rows * res, cols * res])
+    lo, hi = np.array(pos) - L / 2, np.array(pos) + L / 2
+    xy = rng.uniform(lo - 0.6, hi + 0.6, (10000, 2))
+    xy[:1000, 0] = rng.choice([lo[0], hi[0]], 1000)                      # on the map's edges
+    xy[1000:2000, 1] = rng.choice([lo[1], hi[1]], 1000)
+    xy[2000:3000] = lo + res * rng.integers(0, 97, (1000, 2))           # on cell corners
+    for r in (0.1, 0.3, 1.0):
+        got = e.if_blocked(xy, r)
+        want = np.zeros(len(xy), np.uint8)
+        for k in range(len(xy)):
+            c = O.circle_cells(g, tuple(xy[k]), r, reference=REFERENCE)
+            ok = (c[:, 0] >= 0) & (c[:, 0] < rows) & (c[:, 1] >= 0) & (c[:, 1] < cols)
+            want[k] = occ[c[ok, 0] + c[ok, 1] * rows].any()
+        bad = np.flatnonzero(got != want)
+        assert bad.size == 0, (r, xy[bad[:5]], got[bad[:5]])
+        if r == 0.3:
+            og = np.array([O.lib().og_if_blocked(C.byref(g), O.fptr(master), O.d2(*p)) for p in xy], np.uint8)
+            assert np.array_equal(got, og)
+        assert 0 < got.sum() < len(xy)
+    with pytest.raises(R.capi.RnaError):
+        e.if_blocked(xy[:4], -0.1)
+    e.close()
+
+
+def test_radius_range_is_checked(R):
+    e = R.Engine(3.2, 3.2, 0.05)
+    for bad in (-0.01, float("nan"), float("inf"), 64 * 0.05):
+        with pytest.raises(R.capi.RnaError):
+            e.astar_robot_radius(bad)
+    assert e.astar_robot_radius() == 0.0
+    assert e.astar_robot_radius(63 * 0.05) == 63 * 0.05
+    e.close()
+
+
+def test_radius_zero_is_untouched_and_clones_copy_the_radius(R):
+    """r = 0.3 and back to 0 gives the masks of a fresh engine (the point-robot kernels); rna_clone and
+    rna_create_submap carry the radius"""
+    n = 512
+    master = R.synth.obstacles_rect(n, n, density=0.30, seed=2)
+    a = R.Engine(n * 0.05, n * 0.05, 0.05)
+    b = R.Engine(n * 0.05, n * 0.05, 0.05)
+    for e in (a, b):
+        e.upload(R.capi.LAYER_LASER, master)
+        e.compose_master(1)
+    b.astar_robot_radius(0.3)
+    inflated = b.nbr_mask()
+    assert not np.array_equal(inflated, a.nbr_mask())
+    b.astar_robot_radius(0.0)
+    assert np.array_equal(a.nbr_mask(), b.nbr_mask())
+    blocked, nbr = O.astar_masks(master, n, n)
+    assert np.array_equal(b.astar_blocked_mask(), blocked) and np.array_equal(b.nbr_mask(), nbr)
+    q = R.synth.astar_queries(64, master, n, n, seed=5)
+    ra, pa = a.astar(q, 8192)
+    rb, pb = b.astar(q, 8192)
+    assert np.array_equal(ra[["status", "path_len", "cost"]], rb[["status", "path_len", "cost"]]) and np.array_equal(pa, pb)
+    b.astar_robot_radius(0.3)
+    h = C.c_void_p()
+    assert b._L.rna_clone(b.h, C.byref(h)) == 0
+    r = C.c_double(0.0)
+    assert b._L.rna_astar_get_robot_radius(h, C.byref(r)) == 0 and r.value == 0.3
+    out = np.empty(n * n, np.uint8)
+    assert b._L.rna_astar_download_nbr_mask(h, out.ctypes.data, out.size) == 0
+    assert np.array_equal(out, inflated)
+    b._L.rna_destroy(h)
+    sub = b.submap_engine(0.0, 0.0, 6.0, 6.0)
+    assert sub.astar_robot_radius() == 0.3
+    sub.close()
+    a.close()
+    b.close()
