@@ -33,7 +33,9 @@ extern "C" {
  * 5: rna_astar_job_counters (round 6); the default bucket width of the grid search is 128000, a pipeline may have up to 20 stages,
  *    rna_astar_result.rounds counts every job again (also the ones that find nothing); no existing signature changed. */
 /* 6: robot radius of the grid A* (rna_astar_set_robot_radius / _get_robot_radius, rna_astar_download_blocked),
- *    rna_if_blocked_batch[_device], profile slot footprint; no existing signature changed. */
+ *    rna_if_blocked_batch[_device], profile slot footprint; no existing signature changed.
+ * 6, later: goal field entry points added (rna_goal_field_*, rna_goal_field_info), nothing changed -- no signature, no layout,
+ *    no profile slot --, so the version stays 6. */
 #define RNA_ABI_VERSION 6
 
 typedef enum {
@@ -334,6 +336,51 @@ int rna_astar_download_blocked(rna_engine* e, uint8_t* host, size_t n_cells);
  * og_circle_cells and oracle/rrt.c og_if_blocked define them.  The _device form is asynchronous on the engine stream. */
 int rna_if_blocked_batch(rna_engine* e, const double* xy_host, int n, double radius, uint8_t* out_host);
 int rna_if_blocked_batch_device(rna_engine* e, const double* xy_device, int n, double radius, uint8_t* out_device);
+
+/* ---- global planning: goal distance field (one sweep serves every start) ------------------------ */
+/* What navfn / global_planner offer: ONE wavefront expansion from the goal gives the cost-to-goal of every cell, and a plan
+ * from any start is a walk downhill -- for a goal that stays put while robots move (Nav::loopPlan replans to the same goal,
+ * mc/src/nav_node.cpp:103-154) or is shared by a fleet.  Same contract as the batch search (DESIGN.md "Grid A* contract",
+ * oracle/astar.c): the engine's current neighbour masks (what rna_astar_download_nbr_mask returns: robot radius included,
+ * map space on a moved map), costs 1000 / 1414.
+ *   field[c]  least cost of a path between cell c and the goal, int32, indexed by BUFFER linear index; field[goal] = 0;
+ *             RNA_GOAL_FIELD_UNREACHED for blocked cells and cells of other components; cells whose distance is at or
+ *             beyond the search's 30-bit limit (>= 2^30, status 4) read RNA_GOAL_FIELD_FAR; every distance below it is exact.
+ *   next[c]   the canonical step from c towards the goal: neighbour number 0-7 in the contract's fixed order
+ *             (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1) (map space) -- the first neighbour n that c's mask allows
+ *             with field[n] + w == field[c] --, 8 = c is the goal, 254 = far, 255 = unreached.  The flow field a fleet steers by.
+ *   paths     from start s: s, next(s), ..., goal.  Cell for cell the REVERSE of what the batch search answers for the query
+ *             (start = goal, goal = s), cost = field[s].  rna_astar_result: status 0 found (s == goal: path_len 1, cost 0),
+ *             1 field[s] unreached (blocked start, other component, blocked goal), 2 s out of range, 3 path longer than
+ *             max_path_len (path_len = true length), 4 far; expanded = rounds = buckets = 0.
+ * A field is a SNAPSHOT: map updates, rna_move or a new robot radius after the build change neither the field nor the paths
+ * drawn from it; info.stale turns 1 once a call that can change the masks has run (any HIMM batch, compose, upload, fill,
+ * unpack, rna_layer_device_ptr, move or radius call -- conservative), and the next rna_goal_field_build refreshes it.
+ * Memory (5 B per cell) is allocated at the first build; rna_clone / rna_create_submap do not copy a field. */
+#define RNA_GOAL_FIELD_UNREACHED 0x7fffffff
+#define RNA_GOAL_FIELD_FAR       0x7ffffffe
+typedef struct {
+  int32_t goal;        /* buffer linear index the field is rooted at; -1 = no field built yet */
+  int32_t status;      /* 0 built, 2 the goal cell is blocked (every cell unreached) */
+  int32_t reached;     /* cells with a finite distance (the goal included) */
+  int32_t max_cost;    /* largest finite distance */
+  int32_t rounds;      /* relaxation rounds launched */
+  int32_t tile_jobs;   /* tile relaxations run (work inflation = tile_jobs / tiles_reached) */
+  int32_t tiles_reached;   /* 64 x 64 map-space tiles holding a reached cell */
+  int32_t stale;       /* 1 = something that can change the masks ran since the build */
+} rna_goal_field_info;
+/* Builds the field of `goal` on the map stream and returns when it is complete (RNA_ECAPACITY: the relaxation exceeded its
+ * proven round bound or 30 s -- a defect, reported instead of a hang).  Batches in flight on the pipeline stages are not disturbed. */
+int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_info* info_host /* may be NULL */);
+int rna_goal_field_info_get(const rna_engine* e, rna_goal_field_info* out);   /* RNA_OK also before a build (goal -1) */
+/* either pointer may be NULL (not both); RNA_ESTATE before a build */
+int rna_goal_field_download(rna_engine* e, int32_t* field_host, uint8_t* next_host, size_t n_cells);
+void* rna_goal_field_device_ptr(rna_engine* e);   /* int32 per cell, buffer order; NULL before a build */
+/* paths: n x max_path_len cells (row k: the path of starts[k], start first); the _device form is asynchronous on rna_stream() */
+int rna_goal_field_paths(rna_engine* e, const int32_t* starts_host, int n, int32_t* paths_host, int max_path_len,
+                         rna_astar_result* results_host);
+int rna_goal_field_paths_device(rna_engine* e, const int32_t* starts_device, int n, int32_t* paths_device, int max_path_len,
+                                rna_astar_result* results_device);
 
 /* ---- global planning: waypoint-graph A* (the reference's own AStarPlanner) ------------------- */
 /* AStarPlanner::init + makePlan over a caller-supplied graph (astar_planner.cpp:63-145): start and

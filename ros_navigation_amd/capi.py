@@ -36,6 +36,8 @@ SYMBOLS = [
     "rna_astar_configure", "rna_astar_set_pipeline_depth", "rna_astar_set_page_cap", "rna_astar_effective_config", "rna_astar_batch", "rna_astar_batch_device", "rna_astar_settled_counts", "rna_astar_job_counters",
     "rna_astar_download_nbr_mask", "rna_astar_set_robot_radius", "rna_astar_get_robot_radius", "rna_astar_download_blocked",
     "rna_if_blocked_batch", "rna_if_blocked_batch_device",
+    "rna_goal_field_build", "rna_goal_field_info_get", "rna_goal_field_download", "rna_goal_field_device_ptr",
+    "rna_goal_field_paths", "rna_goal_field_paths_device",
     "rna_graph_astar_batch", "rna_rrt_batch", "rna_rrt_batch_device",
     "rna_to_occupancy_grid", "rna_to_occupancy_grid_device", "rna_from_occupancy_grid", "rna_vfh_hist_msg_batch",
     "rna_tailor_plan", "rna_follow_plan", "rna_get_submap", "rna_get_submap_device", "rna_create_submap", "rna_scan_to_rays", "rna_scan_to_rays_device", "rna_scan_projected_beams", "rna_range_to_rays",
@@ -86,6 +88,10 @@ RANGE_READING_TF_DTYPE = np.dtype([("range", "<f4"), ("max_range", "<f4"), ("t",
 ASTAR_QUERY_DTYPE = np.dtype([("start", "<i4"), ("goal", "<i4")])
 ASTAR_RESULT_DTYPE = np.dtype([("status", "<i4"), ("path_len", "<i4"), ("cost", "<i4"), ("expanded", "<i4"),
                                ("rounds", "<i4"), ("buckets", "<i4")])
+# include/rna.h rna_goal_field_info and the two sentinels of a goal distance field
+GOAL_FIELD_INFO_DTYPE = np.dtype([("goal", "<i4"), ("status", "<i4"), ("reached", "<i4"), ("max_cost", "<i4"), ("rounds", "<i4"),
+                                  ("tile_jobs", "<i4"), ("tiles_reached", "<i4"), ("stale", "<i4")])
+GOAL_FIELD_UNREACHED, GOAL_FIELD_FAR = 0x7fffffff, 0x7ffffffe
 RRT_QUERY_DTYPE = np.dtype([("start", "<f8", (2,)), ("target", "<f8", (2,)), ("close_tolerance", "<f8"),
                             ("seed", "<u4"), ("max_samples", "<i4")])
 RRT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("path_len", "<i4"), ("tree_size", "<i4"), ("samples", "<i4")])
@@ -183,6 +189,13 @@ def lib():
     L.rna_if_blocked_batch.argtypes = [vp, vp, C.c_int, C.c_double, vp]
     L.rna_if_blocked_batch_device.argtypes = [vp, vp, C.c_int, C.c_double, vp]
     L.rna_astar_settled_counts.argtypes = [vp, vp, C.c_int]
+    L.rna_goal_field_build.argtypes = [vp, C.c_int32, vp]
+    L.rna_goal_field_info_get.argtypes = [vp, vp]
+    L.rna_goal_field_download.argtypes = [vp, vp, vp, C.c_size_t]
+    L.rna_goal_field_device_ptr.argtypes = [vp]
+    L.rna_goal_field_device_ptr.restype = vp
+    L.rna_goal_field_paths.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
+    L.rna_goal_field_paths_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     if hasattr(L, "rna_astar_job_counters"):   # (absent only in an older build named by the developer switch RNA_LIB of bench.py's A/B runs)
         L.rna_astar_job_counters.argtypes = [vp, vp, C.c_int]
     L.rna_graph_astar_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp]
@@ -633,6 +646,47 @@ class Engine:
 
     def if_blocked_device(self, xy_ptr, n, radius, out_ptr):
         self._check(self._L.rna_if_blocked_batch_device(self.h, xy_ptr, n, float(radius), out_ptr))
+
+    # ---- goal distance field (one sweep from the goal serves every start) ----
+    @staticmethod
+    def _goal_field_info(rec):
+        return {k: int(rec[k][0]) for k in GOAL_FIELD_INFO_DTYPE.names}
+
+    def goal_field(self, goal):
+        """Builds the cost-to-goal field of buffer cell `goal` (rna_goal_field_build); returns the info dict."""
+        info = np.zeros(1, GOAL_FIELD_INFO_DTYPE)
+        self._check(self._L.rna_goal_field_build(self.h, int(goal), _ptr(info)))
+        return self._goal_field_info(info)
+
+    def goal_field_info(self):
+        """rna_goal_field_info of the current field (goal -1 before a build; stale = 1 once the map may have changed)"""
+        info = np.zeros(1, GOAL_FIELD_INFO_DTYPE)
+        self._check(self._L.rna_goal_field_info_get(self.h, _ptr(info)))
+        return self._goal_field_info(info)
+
+    def goal_field_download(self, want_next=False):
+        """The field (int32 per cell, buffer order; GOAL_FIELD_UNREACHED / GOAL_FIELD_FAR); with want_next also the
+        canonical-step bytes (0-7 neighbour number, 8 goal, 254 far, 255 unreached) as a second array."""
+        f = np.empty(self.ncell, np.int32)
+        nx = np.empty(self.ncell, np.uint8) if want_next else None
+        self._check(self._L.rna_goal_field_download(self.h, _ptr(f), _ptr(nx) if want_next else None, f.size))
+        return (f, nx) if want_next else f
+
+    def goal_field_ptr(self):
+        """device pointer of the field (None before a build)"""
+        return self._L.rna_goal_field_device_ptr(self.h)
+
+    def goal_field_paths(self, starts, max_path_len):
+        """Paths start .. goal for a batch of start cells: (paths, results), results as Engine.astar's."""
+        starts = np.ascontiguousarray(starts, np.int32).reshape(-1)
+        n = len(starts)
+        paths = np.zeros((n, max_path_len), np.int32)
+        res = np.zeros(n, ASTAR_RESULT_DTYPE)
+        self._check(self._L.rna_goal_field_paths(self.h, _ptr(starts), n, _ptr(paths), max_path_len, _ptr(res)))
+        return paths, res
+
+    def goal_field_paths_device(self, starts_ptr, n, paths_ptr, max_path_len, results_ptr):
+        self._check(self._L.rna_goal_field_paths_device(self.h, starts_ptr, n, paths_ptr, max_path_len, results_ptr))
 
     def graph_astar(self, vertex_xy, edge_uv, start_target, edge_weight=None, max_len=None):
         v = np.ascontiguousarray(vertex_xy, dtype=np.float64).reshape(-1, 2)

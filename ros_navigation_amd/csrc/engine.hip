@@ -296,6 +296,7 @@ extern "C" void rna_destroy(rna_engine* e) {
   vfh_release(e);
   astar_release(e);
   footprint_release(e);
+  goal_field_release(e);
   for (int l = 0; l < RNA_NUM_LAYERS; ++l) dev_free(&e->layer[l]);
   dev_free(&e->dirty_tiles);
   dev_free(&e->last_dirty);
@@ -324,6 +325,7 @@ extern "C" int rna_get_geometry(const rna_engine* e, rna_geometry* o) {
 }
 
 static void layer_changed(rna_engine* e, int layer) {
+  e->map_epoch++;
   // master written directly (upload, fill, fromOccupancyGrid, a caller's device pointer): it no longer equals laser
   // outside the dirty tiles, so the next compose has to be the reference's whole-layer copy (map_provider.cpp:221)
   if (layer == RNA_LAYER_MASTER) { e->nbr_all_dirty = true; e->master_diverged = true; }
@@ -379,6 +381,7 @@ static int region_copy(rna_engine* e, int layer, int i0, int ni, int j0, int nj,
     if (tracked) {   // per-tile bookkeeping instead of "everything changed": the next compose refreshes these tiles
       const int ta0 = i0 / TILE, ta1 = (i0 + ni - 1) / TILE + 1, tb0 = j0 / TILE, tb1 = (j0 + nj - 1) / TILE + 1;
       const int nt = (ta1 - ta0) * (tb1 - tb0);
+      e->map_epoch++;
       hipLaunchKernelGGL(mark_tiles_kernel, dim3((nt + 255) / 256), dim3(256), 0, e->stream, e->dirty_tiles, e->tiles_i, ta0,
                          ta1, tb0, tb1);
       RNA_HIP(e, hipGetLastError());
@@ -485,6 +488,7 @@ extern "C" int rna_layers_unpack_tiles(rna_engine* e, int layer_a, int layer_b, 
   if (n == 0) return RNA_OK;
   if (!window_ok(e, i0, ni, j0, nj)) return rna::fail(e, RNA_EINVAL, "window outside the map");
   RNA_ENTER(e);
+  e->map_epoch++;
   int rc = stage_tile_list(e, tiles_host, n);
   if (rc != RNA_OK) return rc;
   hipLaunchKernelGGL(unpack_tiles_kernel, dim3(n), dim3(256), 0, e->stream, e->layer[layer_a],
@@ -529,6 +533,7 @@ extern "C" int rna_layers_unpack_tiles_device(rna_engine* e, int layer_a, int la
   if (n == 0) return RNA_OK;
   if (!window_ok(e, i0, ni, j0, nj)) return rna::fail(e, RNA_EINVAL, "window outside the map");
   RNA_ENTER(e);
+  e->map_epoch++;
   hipLaunchKernelGGL(unpack_tiles_kernel, dim3(n), dim3(256), 0, e->stream, e->layer[layer_a],
                      layer_b >= 0 ? e->layer[layer_b] : (float*)nullptr, e->geom.size[0], e->tiles_i, tiles_device, i0,
                      i0 + ni, j0, j0 + nj, dense_device, e->dirty_tiles);
@@ -789,6 +794,7 @@ int map_prepare_nbr(rna_engine* e) {
 extern "C" int rna_compose_master(rna_engine* e, int mode) {
   if (!e || (mode != 0 && mode != 1)) return RNA_EINVAL;
   RNA_ENTER(e);
+  e->map_epoch++;
   const size_t words = ((size_t)e->tiles_i * e->tiles_j + 3) / 4;  // one byte per tile, rounded to words
   const bool full = (mode == 1) || e->laser_all_dirty || e->master_diverged;
   const bool moved = e->geom.start[0] != 0 || e->geom.start[1] != 0;
@@ -849,6 +855,7 @@ extern "C" int rna_compose_master(rna_engine* e, int mode) {
 extern "C" int rna_move(rna_engine* e, double nx, double ny, int* moved) {
   if (!e) return RNA_EINVAL;
   RNA_ENTER(e);
+  e->map_epoch++;
   Geom& g = e->geom;
   const double pshift[2] = {nx - g.pos[0], ny - g.pos[1]};
   int ishift[2];

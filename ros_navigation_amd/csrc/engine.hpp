@@ -135,6 +135,19 @@ struct FootprintPlan {
   int w[64] = {};
 };
 
+// The goal distance field (goal_field.hip): a snapshot of cost-to-goal and canonical steps, built on request.
+struct GoalField {
+  int32_t* field = nullptr;        // [ncell] buffer order: exact distance, RNA_GOAL_FIELD_UNREACHED / _FAR
+  uint8_t* next = nullptr;         // [ncell] neighbour number 0-7 of the canonical step, 8 = goal, 254 = far, 255 = unreached
+  int* keys = nullptr;             // [2][tiles]: pending key per map-space tile, this round's and the next one's
+  uint8_t* touched = nullptr;      // [tiles]: the tile has been relaxed during this build
+  void* ctl = nullptr;             // device control words (GfCtl)
+  void* ctl_host = nullptr;        // their pinned copy
+  int rows = 0, cols = 0, s0 = 0, s1 = 0;   // geometry the field was built with (paths are walked in its map space)
+  unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
+  rna_goal_field_info info{-1, 0, 0, 0, 0, 0, 0, 0};
+};
+
 struct ProfSlot {
   double total_ms = 0;
   int64_t launches = 0;
@@ -173,6 +186,10 @@ struct rna_engine {
   rna::FootprintPlan fp{};           // r > 0: the disc stencil, classified for the geometry's coordinate magnitude
   int2* fp_ties = nullptr;           // r > 0: the tie offsets of fp (device)
   int fp_ties_cap = 0;
+  // counts the calls that can change the neighbour masks (map updates, compose, uploads / fills / unpacks, moves, a new
+  // robot radius): a goal field built at another count reports itself stale
+  unsigned long long map_epoch = 0;
+  rna::GoalField gfield;
   rna::HimmScratch himm;
   rna::VfhDevice vfh;
   rna::AstarDevice astar;
@@ -270,6 +287,7 @@ int map_prepare_nbr(rna_engine* e);   // make e->nbr consistent with the master 
 // or touch a dirty tile (unmoved map), on the engine stream -- the r > 0 replacement of nbr_mask_tiles_kernel
 int footprint_refresh(rna_engine* e, int all);
 int footprint_release(rna_engine* e);
+int goal_field_release(rna_engine* e);
 int sync_all(rna_engine* e);          // main stream + every A* side stream
 // tile-synchronous A* (astar_tile.hip)
 bool tsa_supported(const rna_engine* e);

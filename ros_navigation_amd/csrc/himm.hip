@@ -811,6 +811,7 @@ int himm_launch(rna_engine* e, int layer, const rna_ray* rays_dev, int n) {
     RNA_HIP(e, hipGetLastError());
   }
   if (layer == RNA_LAYER_MASTER) { e->nbr_all_dirty = true; e->master_diverged = true; }
+  e->map_epoch++;
   return RNA_OK;
 }
 

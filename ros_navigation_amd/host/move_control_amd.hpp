@@ -591,6 +591,74 @@ class GridAStarPlanner {
   GridMap& map_;
 };
 
+// The goal distance field of the grid A* (rna_goal_field_*): ONE sweep from the goal gives the cost-to-goal of every cell, and
+// a plan from any start is a walk downhill -- the shape of navfn / global_planner, for a goal that stays put while the robot
+// moves (Nav::loopPlan replans to the same clicked goal, mc/src/nav_node.cpp:103-154) or that a fleet shares.  Plans are cell
+// for cell the ones GridAStarPlanner::makePlan(goal, start) gives, reversed.  The field is a snapshot of the map at the last
+// (re)build: stale() tells when a map update, a move or a new robot radius may have outdated it; rebuild() refreshes it.
+// One field per map (the engine holds it): a second GridGoalField on the same map replaces the first one's field.
+class GridGoalField {
+ public:
+  // builds the field (std::runtime_error when the goal is outside the map or the build fails)
+  GridGoalField(GridMap& map, Position& goal) : map_(map), goal_(goal) {
+    if (!rebuild() && info_.goal < 0) throw std::runtime_error("GridGoalField: goal outside the map");
+  }
+  // false when the goal is outside the map (the old field stays) or its cell is blocked (every start is then unreached)
+  bool rebuild() {
+    grid_map::Index g;
+    if (!map_.getIndex(goal_, g)) return false;
+    grid_map::rna_check(rna_goal_field_build(map_.engine(), g[0] + g[1] * map_.getSize()[0], &info_), map_.engine(), "GridGoalField::rebuild");
+    return info_.status == 0;
+  }
+  bool stale() const {
+    rna_goal_field_info i;
+    grid_map::rna_check(rna_goal_field_info_get(map_.engine(), &i), map_.engine(), "GridGoalField::stale");
+    return i.goal != info_.goal || i.stale != 0;
+  }
+  const rna_goal_field_info& info() const { return info_; }
+  // appends start ... goal cell centres (GridAStarPlanner::makePlan's shape); false when the start is outside the map or
+  // cannot reach the goal.  Cells are placed by the map's CURRENT geometry: rebuild() after a move.
+  bool makePlan(Position& start, std::vector<Position>& path) {
+    grid_map::Index s;
+    if (!map_.getIndex(start, s)) return false;
+    const int rows = map_.getSize()[0];
+    const int32_t cell = s[0] + s[1] * rows;
+    std::vector<int32_t> cells(1 << 16);
+    rna_astar_result r;
+    grid_map::rna_check(rna_goal_field_paths(map_.engine(), &cell, 1, cells.data(), (int)cells.size(), &r), map_.engine(),
+                        "GridGoalField::makePlan");
+    if (r.status == 3) {   // longer than the first buffer: path_len is the true length
+      cells.resize((size_t)r.path_len);
+      grid_map::rna_check(rna_goal_field_paths(map_.engine(), &cell, 1, cells.data(), (int)cells.size(), &r), map_.engine(),
+                          "GridGoalField::makePlan");
+    }
+    if (r.status != 0) return false;
+    for (int k = 0; k < r.path_len; ++k) {
+      Position p;
+      map_.getPosition(grid_map::Index(cells[k] % rows, cells[k] / rows), p);
+      path.push_back(p);
+    }
+    return true;
+  }
+  // 1000 / 1414 integer cost from `start` to the goal; false when outside the map, unreached or beyond the 30-bit range
+  bool costToGoal(Position& start, int32_t& cost) {
+    grid_map::Index s;
+    if (!map_.getIndex(start, s)) return false;
+    const int32_t cell = s[0] + s[1] * map_.getSize()[0];
+    int32_t one = 0;
+    rna_astar_result r;
+    grid_map::rna_check(rna_goal_field_paths(map_.engine(), &cell, 1, &one, 1, &r), map_.engine(), "GridGoalField::costToGoal");
+    if (r.status != 0 && r.status != 3) return false;
+    cost = r.cost;
+    return true;
+  }
+
+ private:
+  GridMap& map_;
+  Position goal_;
+  rna_goal_field_info info_ = {-1, 0, 0, 0, 0, 0, 0, 0};
+};
+
 // RrtPlanner(GridMap&, start, target, closeTolerance).makePlan(path) (rrt_planner.h:17-28): clears
 // then fills `path` goal -> start; returns false (with the best-effort path) after 2000 iterations.
 // Nav::taileredPlan (mc/src/nav_node.cpp:192-204): the plan handed to the Steerer keeps every

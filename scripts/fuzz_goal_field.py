@@ -1,0 +1,142 @@
+"""Developer tool: time-boxed random parity run of the goal distance field (csrc/goal_field.hip) against the CPU oracle:
+the whole field (every cell), reached count, largest distance, and paths (status, cost, length, cells) over random map
+shapes (not multiples of the 64-cell tile), obstacle densities, unknown cells, robot radii, moved maps, goals (blocked
+ones included) and tile-ordering widths.  usage: python scripts/fuzz_goal_field.py [seconds] [seed]
+Exits non-zero on the first mismatch and prints the configuration that reproduces it."""
+import ctypes as C
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch  # noqa: E402  (initialises the HIP runtime before librna.so loads)
+import ros_navigation_amd as R  # noqa: E402
+import _oracle as O  # noqa: E402
+
+UNREACHED = 0x7fffffff
+budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+torch.zeros(1, device="cuda")
+rng = np.random.default_rng(seed)
+t_end = time.time() + budget
+fields = cells = starts_n = found = moved = with_radius = 0
+
+
+def fail(what, here, *more):
+    print("MISMATCH", what, here, *more)
+    sys.exit(1)
+
+
+while time.time() < t_end:
+    rows, cols = int(rng.integers(3, 420)), int(rng.integers(3, 420))
+    if rng.random() < 0.15:
+        rows, cols = int(rng.integers(400, 1100)), int(rng.integers(400, 1100))
+    density = float(rng.choice([0.0, 0.05, 0.2, 0.3, 0.45, 0.6]))
+    side_hi = int(rng.integers(2, max(3, min(rows, cols) // 3 + 2)))
+    mseed = int(rng.integers(0, 1 << 30))
+    master = R.synth.obstacles_rect(rows, cols, density=density, seed=mseed, side=(1, side_hi)).copy()
+    if rng.random() < 0.5:
+        m2 = master.reshape(cols, rows)
+        m2[0, :] = m2[-1, :] = m2[:, 0] = m2[:, -1] = 0.0       # no border wall (it would lie along a moved map's seam)
+    if rng.random() < 0.5:
+        master[rng.random(rows * cols) < 0.05] = np.nan
+    e = R.Engine(rows * 0.05, cols * 0.05, 0.05)
+    g = O.make_geom(rows * 0.05, cols * 0.05, 0.05)
+    assert (e.rows, e.cols) == (rows, cols)
+    for layer in range(3):
+        e.upload(layer, master)
+    ref = master.copy()
+    cfg = dict(rows=rows, cols=cols, density=density, side_hi=side_hi, mseed=mseed, fuzz_seed=seed, field=fields)
+    if rng.random() < 0.4:
+        ptrs = (C.POINTER(C.c_float) * 1)(O.fptr(ref))
+        regs = (O.Region * 4)()
+        mv = C.c_int(0)
+        target = (float(rng.uniform(-0.4, 0.4) * rows * 0.05), float(rng.uniform(-0.4, 0.4) * cols * 0.05))
+        O.lib().og_move(C.byref(g), ptrs, 1, O.d2(*target), regs, C.byref(mv))
+        e.move(*target)
+        e.compose_master(1)
+        assert tuple(e.geometry().start_index) == tuple(g.start), cfg
+        cfg["moved_to"] = target
+        moved += 1
+    if rng.random() < 0.3:
+        r = float(rng.choice([0.05, 0.1, 0.3])) if min(rows, cols) > 20 else 0.05
+        e.astar_robot_radius(r)
+        cfg["radius"] = r
+        with_radius += 1
+    s0, s1 = g.start[0], g.start[1]
+    nbr = e.nbr_mask()                  # pinned against the oracle / the reference by the search's and the footprint's tests
+    blocked = e.astar_blocked_mask()
+
+    def to_map(a):
+        return np.ascontiguousarray(np.roll(np.roll(a.reshape(cols, rows), -s1, axis=0), -s0, axis=1).reshape(-1))
+
+    def lin_to_map(c):
+        return (c % rows - s0) % rows + ((c // rows - s1) % cols) * rows
+
+    def to_buf_cells(p):
+        return ((p % rows + s0) % rows + ((p // rows + s1) % cols) * rows).astype(np.int32)
+
+    nbr_m = to_map(nbr)
+    free = np.flatnonzero(blocked == 0)
+    gw = np.empty(rows * cols, np.int32)
+    if not len(free):
+        e.close()
+        continue
+    for rep in range(int(rng.integers(1, 4))):
+        goal = int(rng.choice(free)) if len(free) and rng.random() < 0.9 else int(rng.integers(0, rows * cols))
+        width = int(rng.choice([0, 3000, 64000, 256000]))
+        os.environ["RNA_GOAL_FIELD_WIDTH"] = str(width)
+        here = dict(cfg, goal=goal, width=width)
+        info = e.goal_field(goal)
+        field, nx = e.goal_field_download(want_next=True)
+        if blocked[goal]:
+            if info["status"] != 2 or info["reached"] != 0 or (field != UNREACHED).any():
+                fail("blocked goal", here, info)
+            continue
+        # the oracle's flood: a search from the goal towards a cell it cannot reach leaves the whole field
+        far = int(np.flatnonzero(to_map(blocked))[0]) if blocked.any() else None
+        if far is None:
+            i, j = np.meshgrid(np.arange(rows), np.arange(cols))
+            gi, gj = lin_to_map(goal) % rows, lin_to_map(goal) // rows
+            dx, dy = np.abs(i - gi), np.abs(j - gj)
+            want_m = (1000 * np.maximum(dx, dy) + 414 * np.minimum(dx, dy)).astype(np.int32).reshape(-1)
+            settled = rows * cols
+        else:
+            ores, _, want_m = O.astar_query(nbr_m, rows, cols, lin_to_map(goal), far, g_work=gw)
+            settled = ores.settled
+        want = np.roll(np.roll(want_m.reshape(cols, rows), s1, axis=0), s0, axis=1).reshape(-1)
+        bad = np.flatnonzero(field != want)
+        if bad.size:
+            fail("field", here, bad[:8], field[bad[:8]], want[bad[:8]])
+        reached = want != UNREACHED
+        if info["reached"] != settled or info["max_cost"] != int(want[reached].max()) or info["status"] != 0:
+            fail("info", here, info, settled)
+        fields += 1
+        cells += rows * cols
+        n = int(rng.integers(1, 40))
+        starts = np.where(rng.random(n) < 0.85, rng.choice(free, n), rng.integers(-2, rows * cols + 2, n)).astype(np.int32)
+        cap = int(rng.choice([rows * cols, 8, 64]))
+        paths, res = e.goal_field_paths(starts, cap)
+        for k in range(n):
+            s = int(starts[k])
+            if s < 0 or s >= rows * cols:
+                ok = res["status"][k] == 2
+            else:
+                o, opath, _ = O.astar_query(nbr_m, rows, cols, lin_to_map(goal), lin_to_map(s), g_work=gw)
+                if o.status != 0:
+                    ok = res["status"][k] == 1
+                else:
+                    ok = res["cost"][k] == o.cost and res["path_len"][k] == o.path_len and res["status"][k] == (3 if o.path_len > cap else 0)
+                    if ok and o.path_len <= cap:
+                        ok = np.array_equal(paths[k, :o.path_len], to_buf_cells(opath[::-1]))
+                        found += 1
+            if not ok:
+                fail("path", here, "start", s, "cap", cap, res[k])
+        starts_n += n
+    e.close()
+print("fuzz ok: %d fields (%d cells) on %d maps moved / %d with a robot radius, %d starts (%d paths compared) in %.0f s, seed %d"
+      % (fields, cells, moved, with_radius, starts_n, found, budget, seed))
