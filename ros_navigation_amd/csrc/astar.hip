@@ -522,10 +522,6 @@ extern "C" int rna_astar_job_counters(rna_engine* e, uint64_t* counters_host, in
   unsigned long long all[16];
   if ((rc = tsa_counters_read(e, all, reset != 0)) != RNA_OK) return rc;
   for (int k = 0; k < 8; ++k) counters_host[k] = all[k];
-#ifdef RNA_TSA_IDLE   /* developer build: wavefront life / idle ticks (shader clock) in the reserved word and the bucket count's */
-  counters_host[6] = all[8];
-  counters_host[7] = all[9];
-#endif
   return RNA_OK;
 }
 

@@ -16,7 +16,7 @@
  *               its own wavefront queues it again with the lowest key when it ends); a free wavefront takes the entry
  *               with the lowest key and drops it if the tile has nothing pending (its wake-ups were consumed already)
  *   round 5: SIM_FIRSTROWS (a tile's first job in a bucket evaluates only the rows that hold a cell the new bound releases --
- *   the rule the kernel's RNA_TSA_FIRST_ROWS implements), SIM_FIRSTWAKE (... and its wake tests take released cells only: no
+ *   the rule the search kernel's first jobs follow), SIM_FIRSTWAKE (... and its wake tests take released cells only: no
  *   difference), SIM_AGAINKEY (a tile woken while it ran is queued with its waker's key instead of the lowest); the last lines
  *   count the re-runs of tiles woken while they ran and how often a wavefront's next tile is the one it just finished -- the
  *   figures behind the kernel's sticky tiles.
