@@ -35,7 +35,9 @@ extern "C" {
 /* 6: robot radius of the grid A* (rna_astar_set_robot_radius / _get_robot_radius, rna_astar_download_blocked),
  *    rna_if_blocked_batch[_device], profile slot footprint; no existing signature changed.
  * 6, later: goal field entry points added (rna_goal_field_*, rna_goal_field_info), nothing changed -- no signature, no layout,
- *    no profile slot --, so the version stays 6. */
+ *    no profile slot --, so the version stays 6.
+ * 6, later still: clearance field and clearance cost (rna_clearance_*, rna_goal_field_set / _get_clearance_cost) added in the
+ *    same way. */
 #define RNA_ABI_VERSION 6
 
 typedef enum {
@@ -381,6 +383,42 @@ int rna_goal_field_paths(rna_engine* e, const int32_t* starts_host, int n, int32
                          rna_astar_result* results_host);
 int rna_goal_field_paths_device(rna_engine* e, const int32_t* starts_device, int n, int32_t* paths_device, int max_path_len,
                                 rna_astar_result* results_device);
+
+/* ---- global planning: clearance field and clearance cost (a costmap's inflation gradient) ------- */
+/* The robot radius above is a hard limit: it closes a narrow door outright and leaves every cell just outside the disc as
+ * cheap as the middle of the corridor.  What costmap_2d's inflation layer adds to navfn / global_planner is the gradient:
+ * cells near obstacles stay passable but cost more, so plans keep their distance where there is room and still squeeze
+ * through where there is none.  Two pieces:
+ *   clr[c]   uint16, indexed by BUFFER linear index: the exact squared Euclidean distance in cells, di^2 + dj^2 (map space,
+ *            unwrapped indices on a moved map), from c to the nearest cell of the search's blocked set -- the set
+ *            rna_astar_download_blocked returns: robot radius included, masks refreshed first in the same way.  Blocked
+ *            cells read 0; cells outside the map are no obstacles (CircleIterator does not visit them either).  The
+ *            transform is capped at max_cells cells, 1 <= max_cells <= 63 (the footprint's bound): a cell with no blocked
+ *            cell at d^2 <= max_cells^2 reads RNA_CLEARANCE_NONE.  Integers only: every value is exact.
+ *   cost     a table cost_by_cells[0 .. n), 2 <= n <= 64, cap R = n - 1: entry k (1 .. R) is the cost in A* cost units of
+ *            BEING ON a free cell with k^2 <= clr < (k + 1)^2; entry 0 is ignored; cells with clr > R^2 (or
+ *            RNA_CLEARANCE_NONE) cost 0.  With a table set, rna_goal_field_build first makes sure a clearance field of that R
+ *            exists for the current masks (it builds one if there is none, if it is stale or if it has another R), then
+ *            computes the least fixpoint of
+ *                field[goal] = 0,   field[c] = pen[c] + min over the neighbours n that c's mask allows of field[n] + w(n, c)
+ *            (the goal's own cost is not counted).  next[c] is the first neighbour in the contract's order with
+ *            field[n] + w + pen[c] == field[c]; paths follow next as before and result.cost = field[start].  A sum at or
+ *            beyond 2^30 is RNA_GOAL_FIELD_FAR as before.  The batch search (rna_astar_batch) does not use the table.
+ * A full rebuild per request; 2 B per cell, allocated at the first build.  `stale` follows the goal field's rule: any call
+ * that can change the masks sets it.  rna_clone / rna_create_submap copy the table, not the fields.  Setting or clearing
+ * the table marks an existing goal field stale (not the clearance field: the masks did not change).  No reference
+ * counterpart: the reference plans on its waypoint graph and checks clearance with the one 0.3 m disc only. */
+#define RNA_CLEARANCE_NONE 0xFFFF
+/* on the map stream; returns when the field is complete.  RNA_EINVAL for max_cells outside 1..63 */
+int rna_clearance_build(rna_engine* e, int max_cells);
+int rna_clearance_download(rna_engine* e, uint16_t* host, size_t n_cells);   /* RNA_ESTATE before a build */
+void* rna_clearance_device_ptr(rna_engine* e);   /* uint16 per cell, buffer order; NULL before a build */
+int rna_clearance_info_get(const rna_engine* e, int* max_cells, int* stale);   /* 0, 0 before a build */
+/* n == 0 (cost_by_cells may be NULL) = off, the default: every goal-field call behaves as without this section.
+ * RNA_EINVAL for any other n outside 2..64.  Host only: takes effect at the next rna_goal_field_build. */
+int rna_goal_field_set_clearance_cost(rna_engine* e, const uint16_t* cost_by_cells, int n);
+/* returns n (0 = off, < 0 = rna_status) and writes the first min(n, cap) entries */
+int rna_goal_field_get_clearance_cost(const rna_engine* e, uint16_t* out, int cap);
 
 /* ---- global planning: waypoint-graph A* (the reference's own AStarPlanner) ------------------- */
 /* AStarPlanner::init + makePlan over a caller-supplied graph (astar_planner.cpp:63-145): start and

@@ -38,6 +38,8 @@ SYMBOLS = [
     "rna_if_blocked_batch", "rna_if_blocked_batch_device",
     "rna_goal_field_build", "rna_goal_field_info_get", "rna_goal_field_download", "rna_goal_field_device_ptr",
     "rna_goal_field_paths", "rna_goal_field_paths_device",
+    "rna_clearance_build", "rna_clearance_download", "rna_clearance_device_ptr", "rna_clearance_info_get",
+    "rna_goal_field_set_clearance_cost", "rna_goal_field_get_clearance_cost",
     "rna_graph_astar_batch", "rna_rrt_batch", "rna_rrt_batch_device",
     "rna_to_occupancy_grid", "rna_to_occupancy_grid_device", "rna_from_occupancy_grid", "rna_vfh_hist_msg_batch",
     "rna_tailor_plan", "rna_follow_plan", "rna_get_submap", "rna_get_submap_device", "rna_create_submap", "rna_scan_to_rays", "rna_scan_to_rays_device", "rna_scan_projected_beams", "rna_range_to_rays",
@@ -92,6 +94,7 @@ ASTAR_RESULT_DTYPE = np.dtype([("status", "<i4"), ("path_len", "<i4"), ("cost", 
 GOAL_FIELD_INFO_DTYPE = np.dtype([("goal", "<i4"), ("status", "<i4"), ("reached", "<i4"), ("max_cost", "<i4"), ("rounds", "<i4"),
                                   ("tile_jobs", "<i4"), ("tiles_reached", "<i4"), ("stale", "<i4")])
 GOAL_FIELD_UNREACHED, GOAL_FIELD_FAR = 0x7fffffff, 0x7ffffffe
+CLEARANCE_NONE = 0xFFFF   # include/rna.h RNA_CLEARANCE_NONE: no blocked cell within the clearance field's cap
 RRT_QUERY_DTYPE = np.dtype([("start", "<f8", (2,)), ("target", "<f8", (2,)), ("close_tolerance", "<f8"),
                             ("seed", "<u4"), ("max_samples", "<i4")])
 RRT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("path_len", "<i4"), ("tree_size", "<i4"), ("samples", "<i4")])
@@ -196,6 +199,13 @@ def lib():
     L.rna_goal_field_device_ptr.restype = vp
     L.rna_goal_field_paths.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     L.rna_goal_field_paths_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
+    L.rna_clearance_build.argtypes = [vp, C.c_int]
+    L.rna_clearance_download.argtypes = [vp, vp, C.c_size_t]
+    L.rna_clearance_device_ptr.argtypes = [vp]
+    L.rna_clearance_device_ptr.restype = vp
+    L.rna_clearance_info_get.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.rna_goal_field_set_clearance_cost.argtypes = [vp, vp, C.c_int]
+    L.rna_goal_field_get_clearance_cost.argtypes = [vp, vp, C.c_int]
     if hasattr(L, "rna_astar_job_counters"):   # (absent only in an older build named by the developer switch RNA_LIB of bench.py's A/B runs)
         L.rna_astar_job_counters.argtypes = [vp, vp, C.c_int]
     L.rna_graph_astar_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp]
@@ -270,6 +280,23 @@ def follow_plan(plan_xy, plan_index, x, y, yaw, linear_velocity=0.0, dt=0.2):
     if rc < 0:
         raise RnaError("rna_follow_plan failed (%d)" % rc)
     return rc == 1, idx.value, pose[0]
+
+
+def inflation_cost_table(resolution, inscribed_radius, inflation_radius, cost_scaling_factor, scale):
+    """costmap_2d's inflation curve as a clearance-cost table for Engine.goal_field_clearance_cost: entry k is
+    round(scale * exp(-cost_scaling_factor * max(0, k * resolution - inscribed_radius))) (halves away from zero) while
+    k * resolution <= inflation_radius, else 0, clipped to 65535.  The table ends with the last such k (at least 2 entries,
+    at most 64: the clearance field's cap is 63 cells).  Entry 0 is not used by the field.  The same arithmetic as
+    move_control::inflationCostTable (move_control_amd.hpp), so both give the same table."""
+    import math
+    n = 1
+    while n < 64 and n * resolution <= inflation_radius:
+        n += 1
+    tab = np.zeros(max(n, 2), np.uint16)
+    for k in range(n):
+        v = scale * math.exp(-cost_scaling_factor * max(0.0, k * resolution - inscribed_radius))
+        tab[k] = int(min(65535.0, max(0.0, math.floor(v + 0.5))))
+    return tab
 
 
 def default_vfh_params():
@@ -687,6 +714,41 @@ class Engine:
 
     def goal_field_paths_device(self, starts_ptr, n, paths_ptr, max_path_len, results_ptr):
         self._check(self._L.rna_goal_field_paths_device(self.h, starts_ptr, n, paths_ptr, max_path_len, results_ptr))
+
+    # ---- clearance field and the goal field's clearance cost ----
+    def clearance(self, max_cells):
+        """Builds the clearance field capped at max_cells (1..63) cells (rna_clearance_build) and returns it: uint16 per cell
+        in buffer order, squared distance in cells to the nearest blocked cell, 0 on blocked cells, CLEARANCE_NONE beyond
+        the cap."""
+        self._check(self._L.rna_clearance_build(self.h, int(max_cells)))
+        return self.clearance_download()
+
+    def clearance_download(self):
+        a = np.empty(self.ncell, np.uint16)
+        self._check(self._L.rna_clearance_download(self.h, _ptr(a), a.size))
+        return a
+
+    def clearance_ptr(self):
+        """device pointer of the clearance field (None before a build)"""
+        return self._L.rna_clearance_device_ptr(self.h)
+
+    def clearance_info(self):
+        """(max_cells, stale) of the clearance field that is there; (0, False) before a build"""
+        r, st = C.c_int(0), C.c_int(0)
+        self._check(self._L.rna_clearance_info_get(self.h, C.byref(r), C.byref(st)))
+        return r.value, bool(st.value)
+
+    def goal_field_clearance_cost(self, table=None):
+        """Sets the clearance-cost table of the goal field when one is given (an empty one turns it off: plain 1000 / 1414
+        fields) and returns the table in force (empty = off).  See inflation_cost_table."""
+        if table is not None:
+            t = np.ascontiguousarray(table, np.uint16).reshape(-1)
+            self._check(self._L.rna_goal_field_set_clearance_cost(self.h, _ptr(t) if len(t) else None, len(t)))
+        out = np.zeros(64, np.uint16)
+        n = self._L.rna_goal_field_get_clearance_cost(self.h, _ptr(out), 64)
+        if n < 0:
+            self._check(n)
+        return out[:n].copy()
 
     def graph_astar(self, vertex_xy, edge_uv, start_target, edge_weight=None, max_len=None):
         v = np.ascontiguousarray(vertex_xy, dtype=np.float64).reshape(-1, 2)

@@ -297,6 +297,7 @@ extern "C" void rna_destroy(rna_engine* e) {
   astar_release(e);
   footprint_release(e);
   goal_field_release(e);
+  clearance_release(e);
   for (int l = 0; l < RNA_NUM_LAYERS; ++l) dev_free(&e->layer[l]);
   dev_free(&e->dirty_tiles);
   dev_free(&e->last_dirty);
@@ -572,6 +573,8 @@ extern "C" int rna_create_submap(rna_engine* parent, double px, double py, doubl
   c->nbr_all_dirty = true;
   c->laser_all_dirty = true;
   c->robot_r = parent->robot_r;
+  c->gfield.cost_n = parent->gfield.cost_n;
+  memcpy(c->gfield.cost_tab, parent->gfield.cost_tab, sizeof(c->gfield.cost_tab));
   *out = c;
   return 1;
 }
@@ -601,6 +604,8 @@ extern "C" int rna_clone(rna_engine* src, rna_engine** out) {
   c->nbr_all_dirty = true;
   c->laser_all_dirty = true;
   c->robot_r = src->robot_r;
+  c->gfield.cost_n = src->gfield.cost_n;
+  memcpy(c->gfield.cost_tab, src->gfield.cost_tab, sizeof(c->gfield.cost_tab));
   *out = c;
   return RNA_OK;
 }

@@ -146,6 +146,19 @@ struct GoalField {
   int rows = 0, cols = 0, s0 = 0, s1 = 0;   // geometry the field was built with (paths are walked in its map space)
   unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
   rna_goal_field_info info{-1, 0, 0, 0, 0, 0, 0, 0};
+  // clearance cost (rna_goal_field_set_clearance_cost): cost_n == 0 = off, the field is the plain 1000 / 1414 one
+  uint16_t cost_tab[64] = {};      // entry k: cost of a free cell with k^2 <= clearance < (k + 1)^2 (entry 0 unused)
+  int cost_n = 0;                  // entries (2..64): the clearance cap is cost_n - 1 cells
+  bool cost_changed = false;       // the table was set or cleared since the build: the field reports itself stale
+  uint16_t* pen = nullptr;         // device: the cost by SQUARED clearance, (cost_n - 1)^2 + 1 entries
+  bool pen_current = false;        // pen holds the present table
+};
+
+// The clearance field (clearance.hip): squared distance of every cell to the nearest blocked cell, built on request.
+struct Clearance {
+  uint16_t* clr = nullptr;         // [ncell] buffer order: di^2 + dj^2, 0 on blocked cells, RNA_CLEARANCE_NONE beyond the cap
+  int R = 0;                       // cap in cells of the field that is there (0 = none)
+  unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
 };
 
 struct ProfSlot {
@@ -190,6 +203,7 @@ struct rna_engine {
   // robot radius): a goal field built at another count reports itself stale
   unsigned long long map_epoch = 0;
   rna::GoalField gfield;
+  rna::Clearance clearance;
   rna::HimmScratch himm;
   rna::VfhDevice vfh;
   rna::AstarDevice astar;
@@ -288,6 +302,9 @@ int map_prepare_nbr(rna_engine* e);   // make e->nbr consistent with the master 
 int footprint_refresh(rna_engine* e, int all);
 int footprint_release(rna_engine* e);
 int goal_field_release(rna_engine* e);
+// clearance field of the current masks capped at R cells, enqueued on the engine stream (clearance.hip)
+int clearance_refresh(rna_engine* e, int R);
+int clearance_release(rna_engine* e);
 int sync_all(rna_engine* e);          // main stream + every A* side stream
 // tile-synchronous A* (astar_tile.hip)
 bool tsa_supported(const rna_engine* e);

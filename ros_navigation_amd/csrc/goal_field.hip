@@ -17,6 +17,10 @@
 //   gf_finalize_kernel  per reached tile: the canonical step of every cell (`next`, the oracle's backtrace rule run over a
 //                       field rooted at the goal), reached cells, largest distance
 //   gf_paths_kernel     one wavefront per start: follows `next` tile by tile through LDS, writes the path start first
+// Clearance cost (rna_goal_field_set_clearance_cost): with a table set the fixpoint is field[c] = pen[c] + min(field[n] + w),
+// pen[c] the table's cost for c's clearance (clearance.hip) -- a non-negative integer per cell, so the least fixpoint is
+// still unique and the same relaxation finds it.  gf_round_kernel<true> / gf_finalize_kernel<true> are that build; the
+// <false> instantiations are the table-free kernels: no penalty load, no extra LDS, the same sweeps as before the table existed.
 // Termination is the host's: it enqueues rounds in chunks, reads the pending count back and stops at zero (rna_goal_field_build).
 // A field is a snapshot: the kernels read the live masks only during the build; paths follow the stored `next` bytes.
 #include "engine.hpp"
@@ -25,6 +29,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <vector>
 
 using namespace rna;
 
@@ -38,6 +43,8 @@ constexpr int GF_S = GF_W + 1;            // LDS row stride (odd: lanes along i 
 constexpr uint8_t GF_NEXT_GOAL = 8, GF_NEXT_FAR = 254, GF_NEXT_NONE = 255;
 constexpr unsigned GF_DEFAULT_WIDTH = 256000;   // see gf_width(): four tiles' worth of cost; 0 / 128 k / 256 k / 512 k measured
 constexpr int GF_CHUNK = 32;              // rounds enqueued between two looks at the pending count
+constexpr int GF_PS = TILE + 1;           // clearance cost of the tile's cells in LDS, uint16: row stride (odd, in halfwords: lanes
+                                          // along j fall into distinct banks as lanes along i do)
 
 // Rotating per-round control words: round r reads slot (r + 2) % 3 (what round r - 1 posted), posts into slot r % 3 and
 // clears slot (r + 1) % 3 for round r + 1.
@@ -93,8 +100,9 @@ __device__ __forceinline__ void gf_load_masks(uint8_t* M, uint8_t* MT, const uin
 
 // one relaxation of tile cell (li, lj), mask m, against its neighbours among DIRS (bit k = neighbour k); 1 when the cell fell.
 // The loads are unconditional (the halo makes every address valid): one LDS round trip per step, not one per neighbour.
+// pen: the cell's clearance cost, paid on entering it (0 without a table).
 template <unsigned DIRS>
-__device__ __forceinline__ int gf_relax(int* F, unsigned m, int li, int lj) {
+__device__ __forceinline__ int gf_relax(int* F, unsigned m, int li, int lj, int pen) {
   m &= DIRS;
   if (!m) return 0;
   int* c = &F[(lj + 1) * GF_S + li + 1];
@@ -103,16 +111,22 @@ __device__ __forceinline__ int gf_relax(int* F, unsigned m, int li, int lj) {
   const int v3 = (DIRS & 8u) ? c[-1] : 0, v4 = (DIRS & 16u) ? c[1] : 0;
   const int v5 = (DIRS & 32u) ? c[GF_S - 1] : 0, v6 = (DIRS & 64u) ? c[GF_S] : 0, v7 = (DIRS & 128u) ? c[GF_S + 1] : 0;
   int best = cur;
-  if (DIRS & 1u) best = min(best, (m & 1u) ? gf_add(v0, 1414) : GF_INF);
-  if (DIRS & 2u) best = min(best, (m & 2u) ? gf_add(v1, 1000) : GF_INF);
-  if (DIRS & 4u) best = min(best, (m & 4u) ? gf_add(v2, 1414) : GF_INF);
-  if (DIRS & 8u) best = min(best, (m & 8u) ? gf_add(v3, 1000) : GF_INF);
-  if (DIRS & 16u) best = min(best, (m & 16u) ? gf_add(v4, 1000) : GF_INF);
-  if (DIRS & 32u) best = min(best, (m & 32u) ? gf_add(v5, 1414) : GF_INF);
-  if (DIRS & 64u) best = min(best, (m & 64u) ? gf_add(v6, 1000) : GF_INF);
-  if (DIRS & 128u) best = min(best, (m & 128u) ? gf_add(v7, 1414) : GF_INF);
+  if (DIRS & 1u) best = min(best, (m & 1u) ? gf_add(v0, 1414 + pen) : GF_INF);
+  if (DIRS & 2u) best = min(best, (m & 2u) ? gf_add(v1, 1000 + pen) : GF_INF);
+  if (DIRS & 4u) best = min(best, (m & 4u) ? gf_add(v2, 1414 + pen) : GF_INF);
+  if (DIRS & 8u) best = min(best, (m & 8u) ? gf_add(v3, 1000 + pen) : GF_INF);
+  if (DIRS & 16u) best = min(best, (m & 16u) ? gf_add(v4, 1000 + pen) : GF_INF);
+  if (DIRS & 32u) best = min(best, (m & 32u) ? gf_add(v5, 1414 + pen) : GF_INF);
+  if (DIRS & 64u) best = min(best, (m & 64u) ? gf_add(v6, 1000 + pen) : GF_INF);
+  if (DIRS & 128u) best = min(best, (m & 128u) ? gf_add(v7, 1414 + pen) : GF_INF);
   if (best < cur) { *c = best; return 1; }
   return 0;
+}
+
+// the clearance cost of a cell: the table by squared clearance, 0 beyond its last entry (RNA_CLEARANCE_NONE included)
+__device__ __forceinline__ int gf_pen(const uint16_t* __restrict__ clr, const uint16_t* __restrict__ pen_tab, int pen_r2, size_t b) {
+  const int c = clr[b];
+  return c <= pen_r2 ? (int)pen_tab[c] : 0;
 }
 
 }  // namespace
@@ -166,11 +180,16 @@ __global__ void gf_seed_kernel(int32_t* __restrict__ field, int* __restrict__ ke
 // advanced two cells per pass: 107 ms per build at 4096^2 instead of the figure in DESIGN.md).  Inside a sweep a cell is
 // written by its owner thread only, reads of cells another wavefront is writing see an earlier or a later valid bound; the
 // two lane layouts are separated by barriers.  Passes repeat until one changes nothing.
+// PEN: the clearance cost of the tile's cells (clr -> pen_tab, see gf_pen) sits in LDS next to the masks, one uint16 layout
+// that both lane orders read without bank conflicts; without PEN the three last arguments are not read.
+template <bool PEN>
 __global__ void __launch_bounds__(256) gf_round_kernel(int32_t* __restrict__ field, const uint8_t* __restrict__ nbr, int* __restrict__ keys,
                                                        uint8_t* __restrict__ touched, GfCtl* __restrict__ ctl, int round, unsigned width,
-                                                       int rows, int cols, int s0, int s1) {
+                                                       int rows, int cols, int s0, int s1, const uint16_t* __restrict__ clr,
+                                                       const uint16_t* __restrict__ pen_tab, int pen_r2) {
   __shared__ int F[GF_W * GF_S];
   __shared__ uint8_t M[TILE * TILE], MT[TILE * TILE];
+  __shared__ uint16_t P[PEN ? TILE * GF_PS : 1];
   __shared__ int wake[8];
   const int tiles_i = gridDim.x, tiles_j = gridDim.y, ntile = tiles_i * tiles_j;
   const int ti = blockIdx.x, tj = blockIdx.y, t = tj * tiles_i + ti;
@@ -201,6 +220,13 @@ __global__ void __launch_bounds__(256) gf_round_kernel(int32_t* __restrict__ fie
   const int i0 = ti * TILE, j0 = tj * TILE;
   gf_load_field(F, field, i0, j0, rows, cols, s0, s1);
   gf_load_masks(M, MT, nbr, i0, j0, rows, cols, s0, s1);
+  if (PEN) {
+    for (int k = threadIdx.x; k < TILE * TILE; k += blockDim.x) {
+      const int pi = k & (TILE - 1), pj = k >> 6;
+      const int i = i0 + pi, j = j0 + pj;
+      P[pj * GF_PS + pi] = (i < rows && j < cols) ? (uint16_t)gf_pen(clr, pen_tab, pen_r2, (size_t)gf_wrap(j, s1, cols) * rows + gf_wrap(i, s0, rows)) : (uint16_t)0;
+    }
+  }
   if (threadIdx.x < 8) wake[threadIdx.x] = GF_INF;
   if (threadIdx.x == 0) {
     touched[t] = 1;
@@ -213,15 +239,15 @@ __global__ void __launch_bounds__(256) gf_round_kernel(int32_t* __restrict__ fie
     changed = 0;
     ++passes;
 #pragma unroll 1
-    for (int s = 0; s < 16; ++s) changed |= gf_relax<0x1Fu>(F, M[(band + s) * TILE + li], li, band + s);        // down: dj = -1, 0
+    for (int s = 0; s < 16; ++s) changed |= gf_relax<0x1Fu>(F, M[(band + s) * TILE + li], li, band + s, PEN ? P[(band + s) * GF_PS + li] : 0);        // down: dj = -1, 0
 #pragma unroll 1
-    for (int s = 15; s >= 0; --s) changed |= gf_relax<0xF8u>(F, M[(band + s) * TILE + li], li, band + s);      // up: dj = 1, 0
+    for (int s = 15; s >= 0; --s) changed |= gf_relax<0xF8u>(F, M[(band + s) * TILE + li], li, band + s, PEN ? P[(band + s) * GF_PS + li] : 0);      // up: dj = 1, 0
     __syncthreads();
     // (li is this thread's j here)
 #pragma unroll 1
-    for (int s = 0; s < 16; ++s) changed |= gf_relax<0x6Bu>(F, MT[(band + s) * TILE + li], band + s, li);       // right: di = -1, 0
+    for (int s = 0; s < 16; ++s) changed |= gf_relax<0x6Bu>(F, MT[(band + s) * TILE + li], band + s, li, PEN ? P[li * GF_PS + band + s] : 0);       // right: di = -1, 0
 #pragma unroll 1
-    for (int s = 15; s >= 0; --s) changed |= gf_relax<0xD6u>(F, MT[(band + s) * TILE + li], band + s, li);     // left: di = 1, 0
+    for (int s = 15; s >= 0; --s) changed |= gf_relax<0xD6u>(F, MT[(band + s) * TILE + li], band + s, li, PEN ? P[li * GF_PS + band + s] : 0);     // left: di = 1, 0
   } while (__syncthreads_or(changed));
   if (threadIdx.x == 0) {
     atomicAdd(&ctl->passes, passes);
@@ -267,10 +293,12 @@ __global__ void __launch_bounds__(256) gf_round_kernel(int32_t* __restrict__ fie
 
 // The canonical step of every cell of a tile that was relaxed: the first neighbour k of the cell's mask (fixed order = lowest
 // map-space linear index first) with field[n] + w == field[c] -- oracle/astar.c's backtrace rule over a field rooted at
-// the goal.  Also the build's totals.
+// the goal.  Also the build's totals.  PEN: field[n] + w + the cell's own clearance cost == field[c].
+template <bool PEN>
 __global__ void __launch_bounds__(256) gf_finalize_kernel(const int32_t* __restrict__ field, const uint8_t* __restrict__ nbr,
                                                           uint8_t* __restrict__ next, const uint8_t* __restrict__ touched,
-                                                          GfCtl* __restrict__ ctl, int goal, int rows, int cols, int s0, int s1) {
+                                                          GfCtl* __restrict__ ctl, int goal, int rows, int cols, int s0, int s1,
+                                                          const uint16_t* __restrict__ clr, const uint16_t* __restrict__ pen_tab, int pen_r2) {
   __shared__ int F[GF_W * GF_S];
   __shared__ int tot[2];
   const int tiles_i = gridDim.x;
@@ -296,11 +324,12 @@ __global__ void __launch_bounds__(256) gf_finalize_kernel(const int32_t* __restr
       if ((int)b == goal) nx = GF_NEXT_GOAL;
       else {
         const unsigned m = nbr[b];
+        const int pen = PEN ? gf_pen(clr, pen_tab, pen_r2, b) : 0;
         const int off[8] = {-GF_S - 1, -GF_S, -GF_S + 1, -1, 1, GF_S - 1, GF_S, GF_S + 1};
         const int wt[8] = {1414, 1000, 1414, 1000, 1000, 1414, 1000, 1414};
 #pragma unroll
         for (int q = 7; q >= 0; --q)
-          if (((m >> q) & 1u) && (unsigned)c[off[q]] < GF_LIMIT && c[off[q]] + wt[q] == v) nx = (uint8_t)q;
+          if (((m >> q) & 1u) && (unsigned)c[off[q]] < GF_LIMIT && c[off[q]] + wt[q] + pen == v) nx = (uint8_t)q;
       }
     }
     next[b] = nx;
@@ -380,6 +409,8 @@ int goal_field_release(rna_engine* e) {
   dev_free(&f.next);
   dev_free(&f.keys);
   dev_free(&f.touched);
+  dev_free(&f.pen);
+  f.pen_current = false;
   if (f.ctl) { (void)hipFree(f.ctl); f.ctl = nullptr; }
   if (f.ctl_host) { (void)hipHostFree(f.ctl_host); f.ctl_host = nullptr; }
   f.info = rna_goal_field_info{-1, 0, 0, 0, 0, 0, 0, 0};
@@ -426,10 +457,28 @@ extern "C" int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_
   if (rc != RNA_OK) return rc;
   if ((rc = gf_alloc(e)) != RNA_OK) return rc;
   GoalField& f = e->gfield;
+  // clearance cost: a clearance field of the table's cap for the current masks, and the table by squared clearance
+  const bool pen = f.cost_n > 0;
+  const int pen_r = f.cost_n - 1, pen_r2 = pen_r * pen_r;
+  if (pen) {
+    if (e->clearance.R != pen_r || e->clearance.epoch != e->map_epoch)
+      if ((rc = clearance_refresh(e, pen_r)) != RNA_OK) return rc;
+    if (!f.pen_current) {
+      std::vector<uint16_t> tab((size_t)pen_r2 + 1, 0);
+      for (int k = 1; k <= pen_r; ++k)
+        for (int d2 = k * k; d2 < (k + 1) * (k + 1) && d2 <= pen_r2; ++d2) tab[d2] = f.cost_tab[k];
+      // (no kernel in flight reads f.pen: a build returns when it is complete, paths do not use it)
+      if ((rc = dev_alloc(e, &f.pen, tab.size())) != RNA_OK) return rc;
+      RNA_HIP(e, hipMemcpy(f.pen, tab.data(), tab.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+      f.pen_current = true;
+    }
+  }
   const Geom& g = e->geom;
   const int rows = g.size[0], cols = g.size[1], s0 = g.start[0], s1 = g.start[1];
   const int ntile = e->tiles_i * e->tiles_j;
-  f.info.goal = -1;   // (no field while this one is being built, also when the build fails)
+  // (no field while this one is being built, also when the build fails from here on; a failure above -- the clearance
+  // refresh, the table upload -- leaves the previous field in place: its buffers have not been touched yet)
+  f.info.goal = -1;
   GfCtl* ctl = static_cast<GfCtl*>(f.ctl);
   GfCtl* host = static_cast<GfCtl*>(f.ctl_host);
   hipLaunchKernelGGL(gf_init_kernel, dim3((unsigned)std::min<size_t>((e->ncell + 255) / 256, 8192)), dim3(256), 0, e->stream, f.field,
@@ -447,8 +496,9 @@ extern "C" int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_
   long long round = 0;
   for (;;) {
     for (int k = 0; k < GF_CHUNK; ++k, ++round)
-      hipLaunchKernelGGL(gf_round_kernel, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream, f.field, e->nbr, f.keys, f.touched, ctl,
-                         (int)(round % 6), width, rows, cols, s0, s1);
+      hipLaunchKernelGGL(pen ? gf_round_kernel<true> : gf_round_kernel<false>, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream,
+                         f.field, e->nbr, f.keys, f.touched, ctl, (int)(round % 6), width, rows, cols, s0, s1,
+                         pen ? e->clearance.clr : (const uint16_t*)nullptr, f.pen, pen_r2);
     RNA_HIP(e, hipGetLastError());
     RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
     RNA_HIP(e, hipStreamSynchronize(e->stream));
@@ -458,13 +508,15 @@ extern "C" int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_
       return fail(e, RNA_ECAPACITY, "rna_goal_field_build: the relaxation did not settle within its bound (" + std::to_string(round) +
                                         " rounds, " + std::to_string(secs) + " s)");
   }
-  hipLaunchKernelGGL(gf_finalize_kernel, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream, f.field, e->nbr, f.next, f.touched, ctl,
-                     goal, rows, cols, s0, s1);
+  hipLaunchKernelGGL(pen ? gf_finalize_kernel<true> : gf_finalize_kernel<false>, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream,
+                     f.field, e->nbr, f.next, f.touched, ctl, goal, rows, cols, s0, s1, pen ? e->clearance.clr : (const uint16_t*)nullptr,
+                     f.pen, pen_r2);
   RNA_HIP(e, hipGetLastError());
   RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
   RNA_HIP(e, hipStreamSynchronize(e->stream));
   f.rows = rows; f.cols = cols; f.s0 = s0; f.s1 = s1;
   f.epoch = e->map_epoch;
+  f.cost_changed = false;
   if (getenv("RNA_GOAL_FIELD_STATS"))   // developer knob
     fprintf(stderr, "[goal field] width %u: %d rounds, %d tile jobs on %d tiles, %d passes (longest job %d)\n", width, host->rounds,
             host->tile_jobs, host->tiles_reached, host->passes, host->max_passes);
@@ -476,8 +528,25 @@ extern "C" int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_
 extern "C" int rna_goal_field_info_get(const rna_engine* e, rna_goal_field_info* out) {
   if (!e || !out) return RNA_EINVAL;
   *out = e->gfield.info;
-  out->stale = (out->goal >= 0 && e->gfield.epoch != e->map_epoch) ? 1 : 0;
+  out->stale = (out->goal >= 0 && (e->gfield.epoch != e->map_epoch || e->gfield.cost_changed)) ? 1 : 0;
   return RNA_OK;
+}
+
+extern "C" int rna_goal_field_set_clearance_cost(rna_engine* e, const uint16_t* cost_by_cells, int n) {
+  if (!e || n < 0 || (n > 0 && (!cost_by_cells || n < 2 || n > 64))) return RNA_EINVAL;
+  GoalField& f = e->gfield;
+  f.cost_n = n;
+  for (int k = 0; k < 64; ++k) f.cost_tab[k] = k < n ? cost_by_cells[k] : (uint16_t)0;
+  f.cost_changed = true;
+  f.pen_current = false;
+  return RNA_OK;
+}
+
+extern "C" int rna_goal_field_get_clearance_cost(const rna_engine* e, uint16_t* out, int cap) {
+  if (!e || cap < 0 || (cap > 0 && !out)) return RNA_EINVAL;
+  const GoalField& f = e->gfield;
+  for (int k = 0; k < f.cost_n && k < cap; ++k) out[k] = f.cost_tab[k];
+  return f.cost_n;
 }
 
 extern "C" int rna_goal_field_download(rna_engine* e, int32_t* field_host, uint8_t* next_host, size_t n_cells) {

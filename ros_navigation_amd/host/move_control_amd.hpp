@@ -207,6 +207,17 @@ class GridMap {
     sm.data.resize((size_t)info.size[0] * info.size[1]);
     return sm;
   }
+  // The clearance field of the grid A* (rna_clearance_build), in BUFFER order like get() and the layers: out[i + j * rows]
+  // for the buffer index (i, j) getIndex hands out (on a moved map that is not the map-space cell: unwrap with
+  // getStartIndex) = squared distance in cells (measured in map space) to the nearest blocked cell of the search (robot
+  // radius included), 0 on blocked cells, RNA_CLEARANCE_NONE where there is none within max_cells (1..63) cells.  What a
+  // costmap's inflation layer is computed from.
+  void clearance(int max_cells, std::vector<uint16_t>& out) {
+    rna_check(rna_clearance_build(e_, max_cells), e_, "GridMap::clearance");
+    rna_geometry g = geometry();
+    out.resize((size_t)g.size[0] * g.size[1]);
+    rna_check(rna_clearance_download(e_, out.data(), out.size()), e_, "GridMap::clearance");
+  }
   rna_engine* engine() const { return e_; }
 
  private:
@@ -597,11 +608,50 @@ class GridAStarPlanner {
 // for cell the ones GridAStarPlanner::makePlan(goal, start) gives, reversed.  The field is a snapshot of the map at the last
 // (re)build: stale() tells when a map update, a move or a new robot radius may have outdated it; rebuild() refreshes it.
 // One field per map (the engine holds it): a second GridGoalField on the same map replaces the first one's field.
+// Clearance cost (rna_goal_field_set_clearance_cost): with a table the field charges every free cell the table's cost for its
+// distance to the nearest obstacle -- costmap_2d's inflation gradient; plans then keep clear of walls where there is room.
+// Like the robot radius it is a setting of the map's engine, shared by every GridGoalField on that map.
+
+// costmap_2d's inflation curve as a clearance-cost table: entry k = lround(scale * exp(-cost_scaling_factor *
+// max(0, k * resolution - inscribed_radius))) while k * resolution <= inflation_radius, else 0, clipped to 65535; the table
+// ends with the last such k (at least 2 entries, at most 64).  capi.py's inflation_cost_table is the same arithmetic.
+inline std::vector<uint16_t> inflationCostTable(double resolution, double inscribed_radius, double inflation_radius,
+                                                double cost_scaling_factor, double scale) {
+  int n = 1;
+  while (n < 64 && n * resolution <= inflation_radius) ++n;
+  std::vector<uint16_t> tab((size_t)(n < 2 ? 2 : n), 0);
+  for (int k = 0; k < n; ++k) {
+    const double d = k * resolution - inscribed_radius;
+    const double v = scale * std::exp(-cost_scaling_factor * (d > 0.0 ? d : 0.0));
+    const double r = std::floor(v + 0.5);
+    tab[k] = (uint16_t)(r > 65535.0 ? 65535.0 : (r > 0.0 ? r : 0.0));
+  }
+  return tab;
+}
+
 class GridGoalField {
  public:
   // builds the field (std::runtime_error when the goal is outside the map or the build fails)
   GridGoalField(GridMap& map, Position& goal) : map_(map), goal_(goal) {
     if (!rebuild() && info_.goal < 0) throw std::runtime_error("GridGoalField: goal outside the map");
+  }
+  // the same with a clearance-cost table (2..64 entries, see setClearanceCost) set before the build
+  GridGoalField(GridMap& map, Position& goal, const std::vector<uint16_t>& clearance_cost) : map_(map), goal_(goal) {
+    setClearanceCost(clearance_cost);
+    if (!rebuild() && info_.goal < 0) throw std::runtime_error("GridGoalField: goal outside the map");
+  }
+  // entry k (1 .. size - 1): cost in A* cost units of a free cell k cells (rounded down) from the nearest obstacle; an empty
+  // table turns the cost off.  The field that is there turns stale(); rebuild() applies the table.
+  void setClearanceCost(const std::vector<uint16_t>& table) {
+    grid_map::rna_check(rna_goal_field_set_clearance_cost(map_.engine(), table.empty() ? nullptr : table.data(), (int)table.size()),
+                        map_.engine(), "GridGoalField::setClearanceCost");
+  }
+  std::vector<uint16_t> clearanceCost() const {
+    std::vector<uint16_t> t(64);
+    const int n = rna_goal_field_get_clearance_cost(map_.engine(), t.data(), (int)t.size());
+    if (n < 0) grid_map::rna_check(n, map_.engine(), "GridGoalField::clearanceCost");
+    t.resize((size_t)n);
+    return t;
   }
   // false when the goal is outside the map (the old field stays) or its cell is blocked (every start is then unreached)
   bool rebuild() {
