@@ -420,6 +420,62 @@ int rna_goal_field_set_clearance_cost(rna_engine* e, const uint16_t* cost_by_cel
 /* returns n (0 = off, < 0 = rna_status) and writes the first min(n, cap) entries */
 int rna_goal_field_get_clearance_cost(const rna_engine* e, uint16_t* out, int cap);
 
+/* ---- global planning: line-of-sight shortcutting of cell paths ----------------------------------- */
+/* Every planner above answers with an 8-connected staircase of cells.  What navfn / global_planner users do after the
+ * search: reduce the plan to the few way points where it has to turn, every straight leg between two of them checked
+ * against the map.  Integers only (DESIGN.md "Grid A* contract" has the full text):
+ *   line(a, b)  the cells of the reference's LineIterator(map, Index start, Index end) between two cells in map space
+ *               (unwrapped indices on a moved map): rna_line_cells_index.
+ *   los(a, b)   every consecutive pair c_t -> c_t+1 of line(a, b) is a move the engine's current neighbour masks allow
+ *               (bit of that move set in nbr[c_t], what rna_astar_download_nbr_mask returns): a leg is itself a path the
+ *               grid-A* contract allows -- robot radius, diagonal corner rule and map space come with the masks.
+ *   shortcut    of a path p[0 .. L): emit p[0]; a = 0; while a < L - 1: k = a + 1; while k + 1 < L and (max_span == 0 or
+ *               k + 1 - a <= max_span) and ok(a, k + 1): k += 1; emit p[k]; a = k.  ok(a, m) = los(p[a], p[m]); with
+ *               RNA_SHORTCUT_KEEP_CLEARANCE additionally min clr over line(p[a], p[m]) >= min clr over p[a .. m] (clr = the
+ *               engine's clearance field, RNA_CLEARANCE_NONE the largest value): a leg never brings the robot closer to an
+ *               obstacle than the piece of plan it replaces.  Visibility along a path is not monotone: the result is
+ *               defined by the FIRST failing candidate, not by the farthest visible cell.  The original step
+ *               p[a] -> p[a + 1] is always accepted, so the way points never drop below the input path.
+ * Input is what rna_astar_batch[_device] / rna_goal_field_paths[_device] leave: rows of max_path_len buffer linear indices
+ * plus the result records (status, path_len); output is rows of max_waypoints buffer linear indices plus one
+ * rna_shortcut_result per path.  The call refreshes the masks first as rna_astar_download_nbr_mask does and uses the
+ * engine's CURRENT geometry.  The _device form is asynchronous on rna_stream(): it chains behind
+ * rna_goal_field_paths_device and behind rna_astar_batch_device without the host seeing a path -- the searches run on the
+ * pipeline stages' own streams, so the call makes rna_stream() wait for every search still in flight (work enqueued on
+ * rna_stream() after it waits with it).  Only searches that ran out of a page share set with rna_astar_set_page_cap get
+ * their second pass from the host: with a page cap, call rna_synchronize() first (a row still at status 5 answers status 1).
+ * The host form returns way-point rows with 0 in every slot behind the last way point (whole rows of 0 for status 1 / 2);
+ * the _device form writes the way points only and leaves the other slots as the caller's buffer had them.
+ * A workgroup's LDS is 4 B x max_path_len -- the row stride, not the longest path -- so a compute unit works on
+ * 160 KiB / (4 x max_path_len) paths at a time: give rows no longer than the plans need.
+ * Cost: an anchor on an open map sees the whole rest of its path, about L^2 / 2 mask bytes per path without max_span and
+ * L * max_span with it -- that is what max_span is for.
+ * RNA_EINVAL: n < 0, max_path_len < 1, max_waypoints < 2, max_span < 0 or == 1 (a span of 1 would be the identity: ask for
+ * 0 = unlimited or >= 2), unknown flag bits, NULL buffers with n > 0.  RNA_ECAPACITY: max_path_len > RNA_SHORTCUT_MAX_PATH_LEN
+ * (a path is staged in the LDS of one compute unit) or a map of more than 65 536 cells along an axis.  RNA_ESTATE:
+ * RNA_SHORTCUT_KEEP_CLEARANCE without a built, non-stale clearance field (rna_clearance_build; the call builds nothing). */
+typedef struct {
+  int32_t status;        /* 0 ok; 1 no input path (input status != 0 or path_len > max_path_len); 2 invalid input path (a cell
+                            out of range, or two consecutive cells that are not king-move neighbours in map space);
+                            3 more way points than max_waypoints (n_waypoints = true count, the first max_waypoints written) */
+  int32_t n_waypoints;   /* start and goal included; a one-cell path gives 1 */
+  int32_t blocked_steps; /* original steps p[t] -> p[t + 1] the current masks do not allow: > 0 = an obstacle has landed on
+                            the plan since it was computed (the replan trigger) */
+  int32_t longest_span;  /* cells of the longest leg (index distance in the input path) */
+} rna_shortcut_result;
+#define RNA_SHORTCUT_KEEP_CLEARANCE 1
+#define RNA_SHORTCUT_MAX_PATH_LEN 40960
+int rna_shortcut_paths(rna_engine* e, const int32_t* paths_host, const rna_astar_result* results_host, int n, int max_path_len,
+                       int max_span, unsigned flags, int32_t* waypoints_host, int max_waypoints, rna_shortcut_result* out_host);
+int rna_shortcut_paths_device(rna_engine* e, const int32_t* paths_device, const rna_astar_result* results_device, int n,
+                              int max_path_len, int max_span, unsigned flags, int32_t* waypoints_device, int max_waypoints,
+                              rna_shortcut_result* out_device);
+/* LineIterator(map, Index start, Index end) (gmc/src/iterators/LineIterator.cpp:25-28, 60-70, 106-150) as a cell list, host
+ * only: raw indices (no geometry, no wrapping), max(|d0|, |d1|) + 1 cells, (i, j) pairs; returns the length of the walk
+ * (only the first `cap` cells are written).  The closed form the shortcut kernel evaluates.  RNA_EINVAL for NULL arguments,
+ * cap < 0 or a coordinate of magnitude 2^30 or more. */
+int rna_line_cells_index(const int32_t start[2], const int32_t end[2], int32_t* cells, int cap);
+
 /* ---- global planning: waypoint-graph A* (the reference's own AStarPlanner) ------------------- */
 /* AStarPlanner::init + makePlan over a caller-supplied graph (astar_planner.cpp:63-145): start and
  * target positions are snapped to the closest vertex; path = start, vertex locations..., target. */
@@ -523,7 +579,8 @@ int rna_from_occupancy_grid(rna_engine* e, int layer, const int8_t* data_host);
 int rna_vfh_hist_msg_batch(rna_engine* e, int n, uint16_t* x_data_host, uint16_t* y_data_host,
                            uint16_t* y_bin_data_host, uint16_t thresholds[2]);
 /* Nav::taileredPlan (mc/src/nav_node.cpp:192-204): walk the plan backwards keeping every stride-th
- * index and the last one (host only; out_xy holds up to n positions). */
+ * index and the last one (host only; out_xy holds up to n positions).  The stride is blind to the map; the map-aware
+ * alternative is rna_shortcut_paths above: the way points where the plan has to turn, every leg checked against the masks. */
 int rna_tailor_plan(const double* plan_xy, int n, unsigned stride, double* out_xy, int* n_out);
 /* Steerer::acceptPlan + the plan-following head of Steerer::update (mc/src/steerer.cpp:27-33,222-256), host only:
  * *plan_index is Steerer::planIndex_ (acceptPlan sets it to 1); way points closer than 250 mm are skipped, then

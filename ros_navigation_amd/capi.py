@@ -40,6 +40,7 @@ SYMBOLS = [
     "rna_goal_field_paths", "rna_goal_field_paths_device",
     "rna_clearance_build", "rna_clearance_download", "rna_clearance_device_ptr", "rna_clearance_info_get",
     "rna_goal_field_set_clearance_cost", "rna_goal_field_get_clearance_cost",
+    "rna_shortcut_paths", "rna_shortcut_paths_device", "rna_line_cells_index",
     "rna_graph_astar_batch", "rna_rrt_batch", "rna_rrt_batch_device",
     "rna_to_occupancy_grid", "rna_to_occupancy_grid_device", "rna_from_occupancy_grid", "rna_vfh_hist_msg_batch",
     "rna_tailor_plan", "rna_follow_plan", "rna_get_submap", "rna_get_submap_device", "rna_create_submap", "rna_scan_to_rays", "rna_scan_to_rays_device", "rna_scan_projected_beams", "rna_range_to_rays",
@@ -56,6 +57,11 @@ class Geometry(C.Structure):
 class SubmapInfo(C.Structure):
     _fields_ = [("length", C.c_double * 2), ("position", C.c_double * 2), ("size", C.c_int32 * 2),
                 ("top_left", C.c_int32 * 2)]
+
+
+class ShortcutResult(C.Structure):
+    """include/rna.h rna_shortcut_result (SHORTCUT_RESULT_DTYPE is the same record for arrays)"""
+    _fields_ = [("status", C.c_int32), ("n_waypoints", C.c_int32), ("blocked_steps", C.c_int32), ("longest_span", C.c_int32)]
 
 
 class VfhParams(C.Structure):
@@ -95,6 +101,10 @@ GOAL_FIELD_INFO_DTYPE = np.dtype([("goal", "<i4"), ("status", "<i4"), ("reached"
                                   ("tile_jobs", "<i4"), ("tiles_reached", "<i4"), ("stale", "<i4")])
 GOAL_FIELD_UNREACHED, GOAL_FIELD_FAR = 0x7fffffff, 0x7ffffffe
 CLEARANCE_NONE = 0xFFFF   # include/rna.h RNA_CLEARANCE_NONE: no blocked cell within the clearance field's cap
+# include/rna.h rna_shortcut_result, the flag and the path-length bound of rna_shortcut_paths
+SHORTCUT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_waypoints", "<i4"), ("blocked_steps", "<i4"), ("longest_span", "<i4")])
+SHORTCUT_KEEP_CLEARANCE = 1
+SHORTCUT_MAX_PATH_LEN = 40960
 RRT_QUERY_DTYPE = np.dtype([("start", "<f8", (2,)), ("target", "<f8", (2,)), ("close_tolerance", "<f8"),
                             ("seed", "<u4"), ("max_samples", "<i4")])
 RRT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("path_len", "<i4"), ("tree_size", "<i4"), ("samples", "<i4")])
@@ -206,6 +216,9 @@ def lib():
     L.rna_clearance_info_get.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.rna_goal_field_set_clearance_cost.argtypes = [vp, vp, C.c_int]
     L.rna_goal_field_get_clearance_cost.argtypes = [vp, vp, C.c_int]
+    L.rna_shortcut_paths.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint, vp, C.c_int, vp]
+    L.rna_shortcut_paths_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint, vp, C.c_int, vp]
+    L.rna_line_cells_index.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
     if hasattr(L, "rna_astar_job_counters"):   # (absent only in an older build named by the developer switch RNA_LIB of bench.py's A/B runs)
         L.rna_astar_job_counters.argtypes = [vp, vp, C.c_int]
     L.rna_graph_astar_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp]
@@ -336,6 +349,13 @@ def _cells(fn, *args):
 def line_cells(g, sx, sy, ex, ey):
     """LineIterator(map, start, end) as a cell list (host only; the cells a HIMM ray clears)"""
     return _cells(lib().rna_line_cells, C.byref(g), sx, sy, ex, ey)
+
+
+def line_cells_index(start, end):
+    """LineIterator(map, Index start, Index end) as a cell list: raw indices, no geometry (host only; the line the
+    shortcut kernel walks between two path cells in map space)"""
+    s, e = (C.c_int32 * 2)(*start), (C.c_int32 * 2)(*end)
+    return _cells(lib().rna_line_cells_index, s, e)
 
 
 def circle_cells(g, cx, cy, radius):
@@ -749,6 +769,35 @@ class Engine:
         if n < 0:
             self._check(n)
         return out[:n].copy()
+
+    # ---- line-of-sight shortcutting of cell paths ----
+    def shortcut_paths(self, paths, results, max_span=0, keep_clearance=False, max_waypoints=None):
+        """Way points of a batch of cell paths (rna_shortcut_paths): `paths` (n x max_path_len buffer cells) and `results`
+        (ASTAR_RESULT_DTYPE) as Engine.astar / Engine.goal_field_paths return them.  Returns (waypoints, results):
+        n x max_waypoints buffer cells (0 behind the last way point) and SHORTCUT_RESULT_DTYPE records.  max_span: longest
+        leg in path cells (0 = unlimited, else >= 2); keep_clearance: no leg comes closer to an obstacle than the piece of
+        path it replaces (needs a current clearance field: Engine.clearance); max_waypoints defaults to max_path_len."""
+        paths = np.ascontiguousarray(paths, np.int32)
+        results = np.ascontiguousarray(results)
+        assert results.dtype == ASTAR_RESULT_DTYPE and paths.ndim == 2 and len(paths) == len(results)
+        n, max_path_len = paths.shape
+        if max_waypoints is None:
+            max_waypoints = max(2, max_path_len)
+        wp = np.zeros((n, max_waypoints), np.int32)
+        out = np.zeros(n, SHORTCUT_RESULT_DTYPE)
+        self._check(self._L.rna_shortcut_paths(self.h, _ptr(paths), _ptr(results), n, max_path_len, int(max_span),
+                                               SHORTCUT_KEEP_CLEARANCE if keep_clearance else 0, _ptr(wp), int(max_waypoints),
+                                               _ptr(out)))
+        return wp, out
+
+    def shortcut_paths_device(self, paths_ptr, results_ptr, n, max_path_len, waypoints_ptr, max_waypoints, out_ptr, max_span=0,
+                              keep_clearance=False):
+        """the same with device pointers, asynchronous on the engine's stream.  Chains behind goal_field_paths_device and behind
+        astar_device without a host synchronisation: the engine's stream is made to wait for the searches still in flight.
+        Only with a page cap (astar_page_cap) synchronize() first: a search out of pages gets its second pass from the host."""
+        self._check(self._L.rna_shortcut_paths_device(self.h, paths_ptr, results_ptr, n, max_path_len, int(max_span),
+                                                      SHORTCUT_KEEP_CLEARANCE if keep_clearance else 0, waypoints_ptr,
+                                                      int(max_waypoints), out_ptr))
 
     def graph_astar(self, vertex_xy, edge_uv, start_target, edge_weight=None, max_len=None):
         v = np.ascontiguousarray(vertex_xy, dtype=np.float64).reshape(-1, 2)

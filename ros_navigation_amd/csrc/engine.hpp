@@ -204,6 +204,7 @@ struct rna_engine {
   unsigned long long map_epoch = 0;
   rna::GoalField gfield;
   rna::Clearance clearance;
+  bool shortcut_lds_raised = false;   // shortcut.hip: the kernels' dynamic-LDS limit has been raised to 160 KiB on this engine's device
   rna::HimmScratch himm;
   rna::VfhDevice vfh;
   rna::AstarDevice astar;

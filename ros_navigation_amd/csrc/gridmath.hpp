@@ -154,6 +154,54 @@ RNA_HD bool submap_information(const Geom& g, const double req_pos[2], const dou
   return true;
 }
 
+// LineIterator(map, Index start, Index end) (gmc/src/iterators/LineIterator.cpp:25-28, 60-70, 106-150) in closed form: the
+// walk is an integer Bresenham over the raw indices, numerator D / 2, one step along the major axis per cell and one along
+// the minor axis whenever the numerator passes D.  After t steps the numerator has been raised by t * A and lowered by D once
+// per minor step, and it stays in [0, D): the minor axis has taken floor((D / 2 + t * A) / D) steps.  D + 1 cells; D == 0 is
+// the single cell.  The host walk (rna_line_cells_index) and the shortcut kernel (shortcut.hip) both evaluate THIS function.
+struct IndexLine {
+  int s[2];      // first cell
+  int step[2];   // +1 / -1 per axis (end >= start: +1, as the reference's increments)
+  int major;     // axis that advances every step: 0 when |d0| >= |d1|
+  int D, A;      // max and min of |d0|, |d1|
+};
+
+RNA_HD IndexLine index_line(const int a[2], const int b[2]) {
+  IndexLine l;
+  const int d0 = b[0] >= a[0] ? b[0] - a[0] : a[0] - b[0], d1 = b[1] >= a[1] ? b[1] - a[1] : a[1] - b[1];
+  l.s[0] = a[0]; l.s[1] = a[1];
+  l.step[0] = b[0] >= a[0] ? 1 : -1;
+  l.step[1] = b[1] >= a[1] ? 1 : -1;
+  l.major = d0 >= d1 ? 0 : 1;
+  l.D = d0 >= d1 ? d0 : d1;
+  l.A = d0 >= d1 ? d1 : d0;
+  return l;
+}
+
+// 1 <= D <= 65535 (so D / 2 + t * A fits 32 bits): steps the minor axis has taken after t steps of the walk, 0 <= t <= D, and
+// the walk's numerator at that cell in `num` -- from there the reference's own increments (num += A; num >= D: num -= D and
+// one minor step) give the following cells without another division, which is how the shortcut kernel walks a turn.
+RNA_HD int index_line_seek32(const IndexLine& l, int t, unsigned& num) {
+  const unsigned x = (unsigned)(l.D / 2) + (unsigned)t * (unsigned)l.A;
+  const unsigned c = x / (unsigned)l.D;
+  num = x - c * (unsigned)l.D;
+  return (int)c;
+}
+
+// steps the minor axis has taken after t steps of the walk, 0 <= t <= D, for any D
+RNA_HD int index_line_minor(const IndexLine& l, int t) {
+  if (l.D == 0) return 0;
+  unsigned num;
+  if (l.D <= 0xFFFF) return index_line_seek32(l, t, num);
+  return (int)(((unsigned long long)(l.D / 2) + (unsigned long long)t * (unsigned long long)l.A) / (unsigned long long)l.D);
+}
+
+RNA_HD void index_line_cell(const IndexLine& l, int t, int out[2]) {
+  const int m = index_line_minor(l, t);
+  out[0] = l.s[0] + l.step[0] * (l.major == 0 ? t : m);
+  out[1] = l.s[1] + l.step[1] * (l.major == 0 ? m : t);
+}
+
 // GridMap::setGeometry (gmc/src/GridMap.cpp:51-70)
 inline void set_geometry(Geom& g, double len_x, double len_y, double res, double px, double py) {
   g.size[0] = (int)round(len_x / res);

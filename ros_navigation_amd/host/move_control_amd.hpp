@@ -257,6 +257,12 @@ class LineIterator : public CellListIterator {      // gmc/src/iterators/LineIte
     const rna_geometry g = map.geometry();
     fill([&](int32_t* c, int cap) { return rna_line_cells(&g, start[0], start[1], end[0], end[1], c, cap); });
   }
+  // LineIterator(map, Index start, Index end) (LineIterator.cpp:25-28): the walk over the raw indices as they are given, no
+  // wrapping -- rna_line_cells_index, the line a shortcut leg is checked along (between two cells in map space)
+  LineIterator(const GridMap&, const Index& start, const Index& end) {
+    const int32_t s[2] = {start[0], start[1]}, e[2] = {end[0], end[1]};
+    fill([&](int32_t* c, int cap) { return rna_line_cells_index(s, e, c, cap); });
+  }
 };
 class CircleIterator : public CellListIterator {    // gmc/src/iterators/CircleIterator.cpp:16-93
  public:
@@ -558,6 +564,44 @@ class AStarPlanner {
   std::vector<int32_t> edges_;
 };
 
+// Line-of-sight shortcutting of a plan (rna_shortcut_paths): `path` -- the cell centres a grid planner's makePlan appended,
+// or any positions whose cells (getIndex) are king-move neighbours one after the other -- is replaced by the way points where
+// it has to turn; every leg between two of them is a line of cells the search's masks allow (robot radius included).
+// max_span: longest leg in path cells (0 = unlimited, else >= 2); keep_clearance: no leg comes closer to an obstacle than the
+// piece of plan it replaces (needs a current clearance field: GridMap::clearance, or a GridGoalField with a clearance cost
+// built since the last map change).  Returns false and leaves `path` alone when it is empty or longer than
+// RNA_SHORTCUT_MAX_PATH_LEN, when a position lies outside the map or when two consecutive cells are not neighbours;
+// blocked_steps (may be NULL) receives the number of original steps the current masks no longer allow: > 0 = replan.
+// The map-aware alternative to taileredPlan's blind stride.
+inline bool shortcutCells(GridMap& map, std::vector<int32_t>& cells, int max_span, bool keep_clearance, int* blocked_steps) {
+  if (cells.empty() || cells.size() > (size_t)RNA_SHORTCUT_MAX_PATH_LEN) return false;
+  const int n = (int)cells.size();
+  rna_astar_result in = {0, n, 0, 0, 0, 0};
+  rna_shortcut_result r;
+  std::vector<int32_t> wp((size_t)(n < 2 ? 2 : n));
+  grid_map::rna_check(rna_shortcut_paths(map.engine(), cells.data(), &in, 1, n, max_span, keep_clearance ? RNA_SHORTCUT_KEEP_CLEARANCE : 0u,
+                                         wp.data(), (int)wp.size(), &r), map.engine(), "shortcutPlan");
+  if (r.status != 0) return false;
+  if (blocked_steps) *blocked_steps = r.blocked_steps;
+  wp.resize((size_t)r.n_waypoints);
+  cells.swap(wp);
+  return true;
+}
+inline bool shortcutPlan(GridMap& map, std::vector<Position>& path, int max_span = 0, bool keep_clearance = false,
+                         int* blocked_steps = nullptr) {
+  const int rows = map.getSize()[0];
+  std::vector<int32_t> cells(path.size());
+  for (size_t k = 0; k < path.size(); ++k) {
+    grid_map::Index c;
+    if (!map.getIndex(path[k], c)) return false;
+    cells[k] = c[0] + c[1] * rows;
+  }
+  if (!shortcutCells(map, cells, max_span, keep_clearance, blocked_steps)) return false;
+  path.resize(cells.size());
+  for (size_t k = 0; k < cells.size(); ++k) map.getPosition(grid_map::Index(cells[k] % rows, cells[k] / rows), path[k]);
+  return true;
+}
+
 // Grid A* over the GridMap's master layer (BASELINE.json's planner): same makePlan shape.
 static_assert(RNA_ABI_VERSION >= 6, "GridAStarPlanner's robot radius needs include/rna.h ABI version 6");
 class GridAStarPlanner {
@@ -590,16 +634,25 @@ class GridAStarPlanner {
     grid_map::rna_check(rna_astar_batch(map_.engine(), &q, 1, cells.data(), (int)cells.size(), &r), map_.engine(),
                         "GridAStarPlanner::makePlan");
     if (r.status != 0) return false;
-    for (int k = 0; k < r.path_len; ++k) {
+    cells.resize((size_t)r.path_len);
+    if (shortcut_ && !shortcutCells(map_, cells, shortcut_span_, shortcut_clearance_, nullptr)) return false;
+    for (size_t k = 0; k < cells.size(); ++k) {
       Position p;
       map_.getPosition(grid_map::Index(cells[k] % rows, cells[k] / rows), p);
       path.push_back(p);
     }
     return true;
   }
+  // Opt-in: makePlan appends the way points of shortcutPlan(max_span, keep_clearance) instead of every cell (off by default;
+  // on = false turns it off again).  keep_clearance needs a current clearance field on the map (GridMap::clearance).
+  void setShortcut(int max_span = 0, bool keep_clearance = false, bool on = true) {
+    shortcut_ = on; shortcut_span_ = max_span; shortcut_clearance_ = keep_clearance;
+  }
 
  private:
   GridMap& map_;
+  bool shortcut_ = false, shortcut_clearance_ = false;
+  int shortcut_span_ = 0;
 };
 
 // The goal distance field of the grid A* (rna_goal_field_*): ONE sweep from the goal gives the cost-to-goal of every cell, and
@@ -683,12 +736,20 @@ class GridGoalField {
                           "GridGoalField::makePlan");
     }
     if (r.status != 0) return false;
-    for (int k = 0; k < r.path_len; ++k) {
+    cells.resize((size_t)r.path_len);
+    if (shortcut_ && !shortcutCells(map_, cells, shortcut_span_, shortcut_clearance_, nullptr)) return false;
+    for (size_t k = 0; k < cells.size(); ++k) {
       Position p;
       map_.getPosition(grid_map::Index(cells[k] % rows, cells[k] / rows), p);
       path.push_back(p);
     }
     return true;
+  }
+  // Opt-in: makePlan appends the way points of shortcutPlan(max_span, keep_clearance) instead of every cell (off by default;
+  // on = false turns it off again).  The legs are checked against the map's CURRENT masks, not the field's snapshot;
+  // keep_clearance needs a current clearance field (a field built with a clearance cost since the last map change has one).
+  void setShortcut(int max_span = 0, bool keep_clearance = false, bool on = true) {
+    shortcut_ = on; shortcut_span_ = max_span; shortcut_clearance_ = keep_clearance;
   }
   // 1000 / 1414 integer cost from `start` to the goal; false when outside the map, unreached or beyond the 30-bit range
   bool costToGoal(Position& start, int32_t& cost) {
@@ -707,6 +768,8 @@ class GridGoalField {
   GridMap& map_;
   Position goal_;
   rna_goal_field_info info_ = {-1, 0, 0, 0, 0, 0, 0, 0};
+  bool shortcut_ = false, shortcut_clearance_ = false;
+  int shortcut_span_ = 0;
 };
 
 // RrtPlanner(GridMap&, start, target, closeTolerance).makePlan(path) (rrt_planner.h:17-28): clears

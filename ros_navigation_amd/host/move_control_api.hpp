@@ -45,6 +45,7 @@ using core::RangeSample;
 typedef core::RrtPlanner RrtPlanner;            // rrt_planner.h:17-28: the signature is the reference's already
 typedef core::GridAStarPlanner GridAStarPlanner;
 using core::taileredPlan;
+using core::shortcutPlan;
 
 class MapProvider;
 class Steerer;
