@@ -476,6 +476,53 @@ int rna_shortcut_paths_device(rna_engine* e, const int32_t* paths_device, const 
  * cap < 0 or a coordinate of magnitude 2^30 or more. */
 int rna_line_cells_index(const int32_t start[2], const int32_t end[2], int32_t* cells, int cap);
 
+/* ---- global planning: exploration frontiers (the goal source of a robot that maps while it drives) -- */
+/* MapUpdater leaves NaN in every cell no ray has crossed and the engine keeps it; a frontier is where the known free space
+ * ends.  Everything in map space (unwrapped indices on a moved map, no adjacency across the map edge), integers and bit
+ * tests only: every output has exactly one right value.
+ *   unknown(c)   the master value of c is NaN (cells outside the map are not unknown)
+ *   free(c)      the master value of c is not NaN and c is not in the search's blocked set -- the set
+ *                rna_astar_download_blocked returns: robot radius included, masks refreshed first in the same way
+ *   frontier(c)  free(c) and at least one of c's four edge neighbours inside the map is unknown
+ *   cluster      an 8-connected component of frontier cells; its label is the smallest BUFFER linear index among its cells
+ *   labels[c]    int32 per cell, indexed by BUFFER linear index: the cluster's label on frontier cells, -1 elsewhere
+ * One rna_frontier per cluster of at least min_size cells, sorted by label.  With RNA_FRONTIER_RANK, cost is the minimum
+ * over the cluster's cells of the engine's goal-field value (compared as the raw int32: RNA_GOAL_FIELD_FAR and _UNREACHED
+ * order themselves) and nearest the cell that has it, ties to the smallest buffer index: build the field at the robot's cell
+ * and cost is the travel cost to the cluster, rna_goal_field_paths from nearest, reversed, the plan to it.  That needs a
+ * built, non-stale goal field (RNA_ESTATE otherwise; the call builds nothing).  Without the flag cost =
+ * RNA_GOAL_FIELD_UNREACHED and nearest = label.  Clusters below min_size get no record; they keep their labels.
+ * A SNAPSHOT like the goal field: later map changes set info.stale (the clearance field's rule) and change nothing else.
+ * Memory: 8 B per cell plus 96 B per cluster, allocated at the first build and released in rna_destroy; rna_clone /
+ * rna_create_submap copy nothing of it.  No reference counterpart: the reference's only goal source is a click in rviz. */
+typedef struct {
+  int32_t label;         /* smallest buffer linear index of the cluster's cells */
+  int32_t size;          /* cells */
+  int32_t min_i, max_i, min_j, max_j;   /* bounding box, map space */
+  int32_t nearest, cost; /* see RNA_FRONTIER_RANK */
+  int64_t sum_i, sum_j;  /* map space: centroid = sum / size */
+} rna_frontier;
+typedef struct {
+  int32_t cells;         /* frontier cells */
+  int32_t clusters_all;  /* clusters before the size filter */
+  int32_t clusters;      /* clusters after the size filter */
+  int32_t largest;       /* size of the largest cluster */
+  int32_t min_size;      /* the value the build was called with */
+  int32_t ranked;        /* 1 = built with RNA_FRONTIER_RANK */
+  int32_t stale;         /* 1 = something that can change the masks ran since the build */
+  int32_t reserved;      /* 0 */
+} rna_frontier_info;
+#define RNA_FRONTIER_RANK 1
+/* On the map stream; returns when complete.  out_host may be NULL iff cap == 0 (count only: RNA_OK).  With cap > 0 and more
+ * clusters than cap: RNA_ECAPACITY, info filled with the true counts, out_host untouched, the labels valid.  RNA_EINVAL:
+ * min_size < 1, cap < 0, unknown flag bits, NULL out_host with cap > 0.  RNA_ECAPACITY also for a map of 2^31 cells or more
+ * and for a kernel that exceeded the stated bound of a loop (a defect, reported instead of a hang). */
+int rna_frontiers_build(rna_engine* e, int min_size, unsigned flags, rna_frontier* out_host, int cap,
+                        rna_frontier_info* info_host /* may be NULL */);
+int rna_frontiers_info_get(const rna_engine* e, rna_frontier_info* out);   /* RNA_OK before a build too (all zero) */
+int rna_frontiers_download(rna_engine* e, int32_t* labels_host, size_t n_cells);   /* RNA_ESTATE before a build */
+void* rna_frontiers_device_ptr(rna_engine* e);   /* int32 per cell, buffer order; NULL before a build */
+
 /* ---- global planning: waypoint-graph A* (the reference's own AStarPlanner) ------------------- */
 /* AStarPlanner::init + makePlan over a caller-supplied graph (astar_planner.cpp:63-145): start and
  * target positions are snapped to the closest vertex; path = start, vertex locations..., target. */

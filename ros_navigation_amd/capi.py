@@ -41,6 +41,7 @@ SYMBOLS = [
     "rna_clearance_build", "rna_clearance_download", "rna_clearance_device_ptr", "rna_clearance_info_get",
     "rna_goal_field_set_clearance_cost", "rna_goal_field_get_clearance_cost",
     "rna_shortcut_paths", "rna_shortcut_paths_device", "rna_line_cells_index",
+    "rna_frontiers_build", "rna_frontiers_info_get", "rna_frontiers_download", "rna_frontiers_device_ptr",
     "rna_graph_astar_batch", "rna_rrt_batch", "rna_rrt_batch_device",
     "rna_to_occupancy_grid", "rna_to_occupancy_grid_device", "rna_from_occupancy_grid", "rna_vfh_hist_msg_batch",
     "rna_tailor_plan", "rna_follow_plan", "rna_get_submap", "rna_get_submap_device", "rna_create_submap", "rna_scan_to_rays", "rna_scan_to_rays_device", "rna_scan_projected_beams", "rna_range_to_rays",
@@ -62,6 +63,18 @@ class SubmapInfo(C.Structure):
 class ShortcutResult(C.Structure):
     """include/rna.h rna_shortcut_result (SHORTCUT_RESULT_DTYPE is the same record for arrays)"""
     _fields_ = [("status", C.c_int32), ("n_waypoints", C.c_int32), ("blocked_steps", C.c_int32), ("longest_span", C.c_int32)]
+
+
+class Frontier(C.Structure):
+    """include/rna.h rna_frontier (FRONTIER_DTYPE is the same record for arrays)"""
+    _fields_ = [("label", C.c_int32), ("size", C.c_int32), ("min_i", C.c_int32), ("max_i", C.c_int32), ("min_j", C.c_int32),
+                ("max_j", C.c_int32), ("nearest", C.c_int32), ("cost", C.c_int32), ("sum_i", C.c_int64), ("sum_j", C.c_int64)]
+
+
+class FrontierInfo(C.Structure):
+    """include/rna.h rna_frontier_info (FRONTIER_INFO_DTYPE is the same record for arrays)"""
+    _fields_ = [("cells", C.c_int32), ("clusters_all", C.c_int32), ("clusters", C.c_int32), ("largest", C.c_int32),
+                ("min_size", C.c_int32), ("ranked", C.c_int32), ("stale", C.c_int32), ("reserved", C.c_int32)]
 
 
 class VfhParams(C.Structure):
@@ -105,6 +118,12 @@ CLEARANCE_NONE = 0xFFFF   # include/rna.h RNA_CLEARANCE_NONE: no blocked cell wi
 SHORTCUT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_waypoints", "<i4"), ("blocked_steps", "<i4"), ("longest_span", "<i4")])
 SHORTCUT_KEEP_CLEARANCE = 1
 SHORTCUT_MAX_PATH_LEN = 40960
+# include/rna.h rna_frontier, rna_frontier_info and the flag of rna_frontiers_build
+FRONTIER_DTYPE = np.dtype([("label", "<i4"), ("size", "<i4"), ("min_i", "<i4"), ("max_i", "<i4"), ("min_j", "<i4"), ("max_j", "<i4"),
+                           ("nearest", "<i4"), ("cost", "<i4"), ("sum_i", "<i8"), ("sum_j", "<i8")])
+FRONTIER_INFO_DTYPE = np.dtype([("cells", "<i4"), ("clusters_all", "<i4"), ("clusters", "<i4"), ("largest", "<i4"), ("min_size", "<i4"),
+                                ("ranked", "<i4"), ("stale", "<i4"), ("reserved", "<i4")])
+FRONTIER_RANK = 1
 RRT_QUERY_DTYPE = np.dtype([("start", "<f8", (2,)), ("target", "<f8", (2,)), ("close_tolerance", "<f8"),
                             ("seed", "<u4"), ("max_samples", "<i4")])
 RRT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("path_len", "<i4"), ("tree_size", "<i4"), ("samples", "<i4")])
@@ -219,6 +238,11 @@ def lib():
     L.rna_shortcut_paths.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint, vp, C.c_int, vp]
     L.rna_shortcut_paths_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_uint, vp, C.c_int, vp]
     L.rna_line_cells_index.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
+    L.rna_frontiers_build.argtypes = [vp, C.c_int, C.c_uint, vp, C.c_int, vp]
+    L.rna_frontiers_info_get.argtypes = [vp, vp]
+    L.rna_frontiers_download.argtypes = [vp, vp, C.c_size_t]
+    L.rna_frontiers_device_ptr.argtypes = [vp]
+    L.rna_frontiers_device_ptr.restype = vp
     if hasattr(L, "rna_astar_job_counters"):   # (absent only in an older build named by the developer switch RNA_LIB of bench.py's A/B runs)
         L.rna_astar_job_counters.argtypes = [vp, vp, C.c_int]
     L.rna_graph_astar_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp]
@@ -798,6 +822,39 @@ class Engine:
         self._check(self._L.rna_shortcut_paths_device(self.h, paths_ptr, results_ptr, n, max_path_len, int(max_span),
                                                       SHORTCUT_KEEP_CLEARANCE if keep_clearance else 0, waypoints_ptr,
                                                       int(max_waypoints), out_ptr))
+
+    # ---- exploration frontiers ----
+    @staticmethod
+    def _frontier_info(rec):
+        return {k: int(rec[k][0]) for k in FRONTIER_INFO_DTYPE.names}
+
+    def frontiers(self, min_size=1, rank=False, cap=4096):
+        """Detects, clusters and (rank=True: by the current goal field) ranks the exploration frontiers of the master layer
+        (rna_frontiers_build).  Returns (records, info): FRONTIER_DTYPE records of the clusters of at least min_size cells,
+        sorted by label, and the info dict.  cap = 0 only counts (no records).  Raises RnaError with the true count when
+        there are more clusters than cap; the labels (Engine.frontier_labels) are valid all the same."""
+        recs = np.zeros(int(cap), FRONTIER_DTYPE)
+        info = np.zeros(1, FRONTIER_INFO_DTYPE)
+        self._check(self._L.rna_frontiers_build(self.h, int(min_size), FRONTIER_RANK if rank else 0, _ptr(recs) if cap else None,
+                                                int(cap), _ptr(info)))
+        d = self._frontier_info(info)
+        return recs[:d["clusters"]].copy(), d
+
+    def frontier_labels(self):
+        """int32 per cell in buffer order: the cluster's label (its smallest buffer index) on frontier cells, -1 elsewhere"""
+        a = np.empty(self.ncell, np.int32)
+        self._check(self._L.rna_frontiers_download(self.h, _ptr(a), a.size))
+        return a
+
+    def frontier_labels_ptr(self):
+        """device pointer of the labels (None before a build)"""
+        return self._L.rna_frontiers_device_ptr(self.h)
+
+    def frontiers_info(self):
+        """rna_frontier_info of the snapshot that is there (all zero before a build; stale = 1 once the map may have changed)"""
+        info = np.zeros(1, FRONTIER_INFO_DTYPE)
+        self._check(self._L.rna_frontiers_info_get(self.h, _ptr(info)))
+        return self._frontier_info(info)
 
     def graph_astar(self, vertex_xy, edge_uv, start_target, edge_weight=None, max_len=None):
         v = np.ascontiguousarray(vertex_xy, dtype=np.float64).reshape(-1, 2)

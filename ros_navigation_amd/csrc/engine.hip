@@ -298,6 +298,7 @@ extern "C" void rna_destroy(rna_engine* e) {
   footprint_release(e);
   goal_field_release(e);
   clearance_release(e);
+  frontiers_release(e);
   for (int l = 0; l < RNA_NUM_LAYERS; ++l) dev_free(&e->layer[l]);
   dev_free(&e->dirty_tiles);
   dev_free(&e->last_dirty);

@@ -161,6 +161,20 @@ struct Clearance {
   unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
 };
 
+// Exploration frontiers (frontier.hip): labels of the 8-connected clusters of frontier cells and their records, built on request.
+struct Frontiers {
+  int32_t* labels = nullptr;       // [ncell] buffer order: the cluster's smallest buffer index on frontier cells, -1 elsewhere
+  int32_t* slot = nullptr;         // [ncell] written at root cells only: the root's entry of rec
+  rna_frontier* rec = nullptr;     // [rec_cap] one accumulator per cluster, in arrival order
+  rna_frontier* out = nullptr;     // [rec_cap] the records that passed the size filter
+  int rec_cap = 0;
+  void* ctl = nullptr;             // device control words (FrCtl)
+  void* ctl_host = nullptr;        // their pinned copy
+  bool built = false;
+  unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
+  rna_frontier_info info{0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 struct ProfSlot {
   double total_ms = 0;
   int64_t launches = 0;
@@ -204,6 +218,7 @@ struct rna_engine {
   unsigned long long map_epoch = 0;
   rna::GoalField gfield;
   rna::Clearance clearance;
+  rna::Frontiers frontiers;
   bool shortcut_lds_raised = false;   // shortcut.hip: the kernels' dynamic-LDS limit has been raised to 160 KiB on this engine's device
   rna::HimmScratch himm;
   rna::VfhDevice vfh;
@@ -306,6 +321,7 @@ int goal_field_release(rna_engine* e);
 // clearance field of the current masks capped at R cells, enqueued on the engine stream (clearance.hip)
 int clearance_refresh(rna_engine* e, int R);
 int clearance_release(rna_engine* e);
+int frontiers_release(rna_engine* e);
 int sync_all(rna_engine* e);          // main stream + every A* side stream
 // tile-synchronous A* (astar_tile.hip)
 bool tsa_supported(const rna_engine* e);

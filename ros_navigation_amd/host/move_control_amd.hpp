@@ -17,6 +17,7 @@
 // Data lives on the GPU inside one rna_engine; these classes own no algorithmic code.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstddef>
@@ -602,6 +603,56 @@ inline bool shortcutPlan(GridMap& map, std::vector<Position>& path, int max_span
   return true;
 }
 
+// Exploration frontiers (rna_frontiers_build): where the known free space of the map ends -- free cells (not NaN, not in the
+// search's blocked set, robot radius included) with an unknown (NaN) edge neighbour --, clustered by 8-connectivity.  The goal
+// source of a robot that maps while it drives: the reference's only one is a click in rviz.
+struct Frontier {
+  grid_map::Index label, nearest;   // cells as getIndex returns them: the cluster's cell with the smallest buffer linear index,
+                                    // and its cell of least cost (== label when not ranked)
+  Position centroid;                // mean of the cells' centres (it need not lie on a frontier cell, nor on a free one)
+  int size;                         // cells
+  int cost;                         // 1000 / 1414 travel cost to `nearest` (RNA_GOAL_FIELD_UNREACHED when not ranked or out of reach)
+  grid_map::Index min, max;         // bounding box in MAP space: indices counted from the map's present top-left corner
+};
+inline void frontierRecords(GridMap& map, int min_size, bool rank, std::vector<Frontier>& out, const char* who) {
+  std::vector<rna_frontier> recs(1024);
+  rna_frontier_info info = {0, 0, 0, 0, 0, 0, 0, 0};
+  const unsigned flags = rank ? RNA_FRONTIER_RANK : 0u;
+  int rc = rna_frontiers_build(map.engine(), min_size, flags, recs.data(), (int)recs.size(), &info);
+  if (rc == RNA_ECAPACITY && info.clusters > (int)recs.size()) {   // more clusters than the first buffer: info has the true count
+    recs.resize((size_t)info.clusters);
+    rc = rna_frontiers_build(map.engine(), min_size, flags, recs.data(), (int)recs.size(), &info);
+  }
+  grid_map::rna_check(rc, map.engine(), who);
+  const int rows = map.getSize()[0], cols = map.getSize()[1];
+  const grid_map::Index start = map.getStartIndex();
+  const double res = map.getResolution();
+  out.clear();
+  out.reserve((size_t)info.clusters);
+  for (int k = 0; k < info.clusters; ++k) {
+    const rna_frontier& r = recs[(size_t)k];
+    Frontier f;
+    f.label = grid_map::Index(r.label % rows, r.label / rows);
+    f.nearest = grid_map::Index(r.nearest % rows, r.nearest / rows);
+    f.size = r.size;
+    f.cost = r.cost;
+    f.min = grid_map::Index(r.min_i, r.min_j);
+    f.max = grid_map::Index(r.max_i, r.max_j);
+    // the label cell's centre, moved by the centroid's offset from it in map space (positions fall as indices grow)
+    Position p;
+    map.getPosition(f.label, p);
+    const int li = (f.label[0] - start[0] + rows) % rows, lj = (f.label[1] - start[1] + cols) % cols;
+    f.centroid = Position(p[0] - ((double)r.sum_i / r.size - li) * res, p[1] - ((double)r.sum_j / r.size - lj) * res);
+    out.push_back(f);
+  }
+}
+// every cluster of at least min_size cells, sorted by label (buffer linear index); false for min_size < 1
+inline bool findFrontiers(GridMap& map, int min_size, std::vector<Frontier>& out) {
+  if (min_size < 1) return false;
+  frontierRecords(map, min_size, false, out, "findFrontiers");
+  return true;
+}
+
 // Grid A* over the GridMap's master layer (BASELINE.json's planner): same makePlan shape.
 static_assert(RNA_ABI_VERSION >= 6, "GridAStarPlanner's robot radius needs include/rna.h ABI version 6");
 class GridAStarPlanner {
@@ -750,6 +801,18 @@ class GridGoalField {
   // keep_clearance needs a current clearance field (a field built with a clearance cost since the last map change has one).
   void setShortcut(int max_span = 0, bool keep_clearance = false, bool on = true) {
     shortcut_ = on; shortcut_span_ = max_span; shortcut_clearance_ = keep_clearance;
+  }
+  // Exploration: with the field rooted at the ROBOT's cell, cost-to-goal is the travel cost to every cell -- the frontiers of
+  // the map ranked by it, `out` sorted by (cost, label): out[0].nearest is the cheapest place where the known space ends and
+  // makePlan from its centre, reversed, the plan to it.  false (and `out` untouched) for min_size < 1 or a stale() field.
+  bool frontiers(int min_size, std::vector<Frontier>& out) {
+    if (min_size < 1 || stale()) return false;
+    frontierRecords(map_, min_size, true, out, "GridGoalField::frontiers");
+    std::sort(out.begin(), out.end(), [this](const Frontier& a, const Frontier& b) {
+      const int rows = map_.getSize()[0];
+      return a.cost != b.cost ? a.cost < b.cost : a.label[0] + a.label[1] * rows < b.label[0] + b.label[1] * rows;
+    });
+    return true;
   }
   // 1000 / 1414 integer cost from `start` to the goal; false when outside the map, unreached or beyond the 30-bit range
   bool costToGoal(Position& start, int32_t& cost) {

@@ -46,6 +46,9 @@ typedef core::RrtPlanner RrtPlanner;            // rrt_planner.h:17-28: the sign
 typedef core::GridAStarPlanner GridAStarPlanner;
 using core::taileredPlan;
 using core::shortcutPlan;
+using core::Frontier;
+using core::findFrontiers;
+typedef core::GridGoalField GridGoalField;   // (its frontiers() ranks them)
 
 class MapProvider;
 class Steerer;
