@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402  (initialises the HIP runtime before librna.so loads)
 import ros_navigation_amd as R  # noqa: E402
 import test_gpu_frontiers as T  # noqa: E402
+from _gpu import to_buffer  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
@@ -57,7 +58,7 @@ while time.time() < t_end:
         moved += 1
     g = e.geometry()
     m = T.serpentine(rows, cols, int(rng.integers(2, 5))) if rng.random() < 0.1 else random_map(rows, cols, rng)
-    e.upload(R.capi.LAYER_MASTER, T.to_buffer(m, rows, cols, g.start_index[0], g.start_index[1]))
+    e.upload(R.capi.LAYER_MASTER, to_buffer(m, rows, cols, g.start_index[0], g.start_index[1]))
     if rng.random() < 0.4:
         cfg["radius"] = float(rng.choice([0.05, 0.15, 0.3]))
         e.astar_robot_radius(cfg["radius"])

@@ -16,8 +16,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402  (initialises the HIP runtime before librna.so loads)
 import ros_navigation_amd as R  # noqa: E402
 import _oracle as O  # noqa: E402
+from _gpu import UNREACHED, to_buffer, to_map  # noqa: E402
 
-UNREACHED = 0x7fffffff
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 torch.zeros(1, device="cuda")
@@ -71,8 +71,8 @@ while time.time() < t_end:
     nbr = e.nbr_mask()                  # pinned against the oracle / the reference by the search's and the footprint's tests
     blocked = e.astar_blocked_mask()
 
-    def to_map(a):
-        return np.ascontiguousarray(np.roll(np.roll(a.reshape(cols, rows), -s1, axis=0), -s0, axis=1).reshape(-1))
+    def flat_map(a):
+        return np.ascontiguousarray(to_map(a, rows, cols, s0, s1).reshape(-1))
 
     def lin_to_map(c):
         return (c % rows - s0) % rows + ((c // rows - s1) % cols) * rows
@@ -80,7 +80,7 @@ while time.time() < t_end:
     def to_buf_cells(p):
         return ((p % rows + s0) % rows + ((p // rows + s1) % cols) * rows).astype(np.int32)
 
-    nbr_m = to_map(nbr)
+    nbr_m = flat_map(nbr)
     free = np.flatnonzero(blocked == 0)
     gw = np.empty(rows * cols, np.int32)
     if not len(free):
@@ -98,7 +98,7 @@ while time.time() < t_end:
                 fail("blocked goal", here, info)
             continue
         # the oracle's flood: a search from the goal towards a cell it cannot reach leaves the whole field
-        far = int(np.flatnonzero(to_map(blocked))[0]) if blocked.any() else None
+        far = int(np.flatnonzero(flat_map(blocked))[0]) if blocked.any() else None
         if far is None:
             i, j = np.meshgrid(np.arange(rows), np.arange(cols))
             gi, gj = lin_to_map(goal) % rows, lin_to_map(goal) // rows
@@ -108,7 +108,7 @@ while time.time() < t_end:
         else:
             ores, _, want_m = O.astar_query(nbr_m, rows, cols, lin_to_map(goal), far, g_work=gw)
             settled = ores.settled
-        want = np.roll(np.roll(want_m.reshape(cols, rows), s1, axis=0), s0, axis=1).reshape(-1)
+        want = to_buffer(want_m, rows, cols, s0, s1)
         bad = np.flatnonzero(field != want)
         if bad.size:
             fail("field", here, bad[:8], field[bad[:8]], want[bad[:8]])

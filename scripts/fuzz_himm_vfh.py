@@ -16,15 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 import ros_navigation_amd as R  # noqa: E402
 import _oracle as O  # noqa: E402
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same_f32(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(bits(a)[~np.isnan(a)], bits(b)[~np.isnan(b)])
+from _gpu import bits, same_f32  # noqa: E402
 
 
 def gen_rays(rng, n, g, lx, ly, res):

@@ -19,7 +19,8 @@ import torch  # noqa: E402
 import ros_navigation_amd as R  # noqa: E402
 from ros_navigation_amd.dist import TileLayout  # noqa: E402
 import _oracle as O  # noqa: E402
-from fuzz_himm_vfh import gen_rays, same_f32  # noqa: E402
+from _gpu import same_f32  # noqa: E402
+from fuzz_himm_vfh import gen_rays  # noqa: E402
 
 
 def main():

@@ -8,15 +8,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from _build import capi  # noqa: F401  (the fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import _build
-    _build.native()
-    from ros_navigation_amd import capi
-    return capi
 
 
 def header_symbols():

@@ -4,30 +4,15 @@ header, a compiled C snippet and the Python mirror, the ABI version and the prof
 need no device, the C++ additions compile and link, the inflation curve is the same table in C++ and in Python, and the
 kernels' resource budgets on gfx950."""
 import ctypes as C
-import os
-import re
 import subprocess
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ros_navigation_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
-HPP = os.path.join(ROOT, "ros_navigation_amd", "host", "move_control_amd.hpp")
-LIB_DIR = os.path.join(ROOT, "ros_navigation_amd")
-HIPCC = "/opt/rocm/bin/hipcc"
+from _build import HPP, LIB_DIR, c_values, capi, needs_hipcc, resources  # noqa: F401  (capi: the fixture)
+
 NEW = ["rna_clearance_build", "rna_clearance_download", "rna_clearance_device_ptr", "rna_clearance_info_get",
        "rna_goal_field_set_clearance_cost", "rna_goal_field_get_clearance_cost"]
 RNA_EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import _build
-    _build.native()
-    from ros_navigation_amd import capi
-    return capi
 
 
 def test_new_symbols_are_exported_and_bound(capi):
@@ -42,19 +27,9 @@ def test_new_symbols_are_exported_and_bound(capi):
 
 
 def test_sentinel_abi_version_and_profile_slots(capi, tmp_path):
-    src = tmp_path / "none.c"
-    src.write_text(r'''
-#include <stdio.h>
-#include "rna.h"
-int main(void) {
+    got = c_values(tmp_path, r'''
   uint16_t v = RNA_CLEARANCE_NONE;
-  printf("%d %d %d %d\n", RNA_CLEARANCE_NONE, (int)v, RNA_ABI_VERSION, (int)RNA_K_COUNT);
-  return 0;
-}
-''')
-    exe = tmp_path / "none"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-I" + INCLUDE, str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+  printf("%d %d %d %d\n", RNA_CLEARANCE_NONE, (int)v, RNA_ABI_VERSION, (int)RNA_K_COUNT);''')
     assert got[0] == got[1] == capi.CLEARANCE_NONE == 0xFFFF
     assert got[2] == 6 == capi.ABI_VERSION == capi.lib().rna_abi_version()      # entry points were added, nothing changed
     assert got[3] == len(capi.KERNELS) and capi.KERNELS[-1] == "footprint"      # no new profile slot
@@ -149,25 +124,7 @@ int main() {
     assert list(capi.inflation_cost_table(*PARAMS[3])) == [900, 0]
 
 
-def resources(src):
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-c",
-                          os.path.join(CSRC, src), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-        for key in ("VGPRs", r"LDS Size \[bytes/block\]", r"ScratchSize \[bytes/lane\]"):
-            m = re.search(r"remark:\s+" + key + r": (\d+)", line)
-            if m and name:
-                res[name][key.split(" ")[0]] = int(m.group(1))
-    return res
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@needs_hipcc
 def test_kernel_budgets():
     """clearance.hip: no kernel uses scratch; the tile kernel (one 256-thread workgroup per 64 x 64 tile, the blocked bits of
     the tile with a 63-cell halo in LDS) stays inside the footprint kernel's own budget, LDS <= 16 KiB and VGPRs <= 64.

@@ -6,22 +6,11 @@ import os
 import re
 import subprocess
 
-import pytest
+from _build import HPP, INCLUDE, LIB_DIR, capi, needs_hipcc, resources  # noqa: F401  (capi: the fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ros_navigation_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 NEW = ["rna_astar_set_robot_radius", "rna_astar_get_robot_radius", "rna_astar_download_blocked", "rna_if_blocked_batch",
        "rna_if_blocked_batch_device"]
 RNA_EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import _build
-    _build.native()
-    from ros_navigation_amd import capi
-    return capi
 
 
 def test_new_symbols_are_exported_and_bound(capi):
@@ -33,10 +22,10 @@ def test_new_symbols_are_exported_and_bound(capi):
 
 
 def test_abi_version_is_6_everywhere(capi):
-    hdr = open(os.path.join(ROOT, "include", "rna.h")).read()
+    hdr = open(os.path.join(INCLUDE, "rna.h")).read()
     assert int(re.search(r"#define RNA_ABI_VERSION (\d+)", hdr).group(1)) == 6
     assert capi.ABI_VERSION == 6 and capi.lib().rna_abi_version() == 6
-    hpp = open(os.path.join(ROOT, "ros_navigation_amd", "host", "move_control_amd.hpp")).read()
+    hpp = open(HPP).read()
     assert "RNA_ABI_VERSION >= 6" in hpp
 
 
@@ -74,31 +63,17 @@ int main(int argc, char**) {
   (void)make;
   return 0;
 }
-''' % os.path.join(ROOT, "ros_navigation_amd", "host", "move_control_amd.hpp"))
-    lib_dir = os.path.join(ROOT, "ros_navigation_amd")
-    subprocess.check_call(["g++", "-std=c++11", "-Wall", str(src), "-o", str(tmp_path / "planner_radius"), "-L" + lib_dir, "-lrna",
-                           "-Wl,-rpath," + lib_dir, "-lpthread"])
+''' % HPP)
+    subprocess.check_call(["g++", "-std=c++11", "-Wall", str(src), "-o", str(tmp_path / "planner_radius"), "-L" + LIB_DIR, "-lrna",
+                           "-Wl,-rpath," + LIB_DIR, "-lpthread"])
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@needs_hipcc
 def test_footprint_kernel_budget():
     """footprint_tiles_kernel (one 256-thread workgroup per 64 x 64 tile) and the if_blocked kernel compile for gfx950
     without scratch; the tile kernel's LDS (occupancy bits of the tile with a 64-cell halo + its blocked bytes) stays
     small enough for many workgroups per CU."""
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-c",
-                          os.path.join(CSRC, "footprint.hip"), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-        for key in ("VGPRs", r"LDS Size \[bytes/block\]", r"ScratchSize \[bytes/lane\]"):
-            m = re.search(r"remark:\s+" + key + r": (\d+)", line)
-            if m and name:
-                res[name][key.split(" ")[0]] = int(m.group(1))
+    res = resources("footprint.hip")
     tiles = next(v for k, v in res.items() if "footprint_tiles_kernel" in k)
     point = next(v for k, v in res.items() if "if_blocked_kernel" in k)
     assert tiles["ScratchSize"] == 0 and point["ScratchSize"] == 0, res

@@ -4,28 +4,15 @@ profile slots did not move, argument checks that need no device, the kernels' re
 additions compile and link."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ros_navigation_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
-HOST = os.path.join(ROOT, "ros_navigation_amd", "host")
-LIB_DIR = os.path.join(ROOT, "ros_navigation_amd")
-HIPCC = "/opt/rocm/bin/hipcc"
+from _build import (HOST, INCLUDE, LIB_DIR, c_values, capi, needs_hipcc, resources,  # noqa: F401  (capi: the fixture)
+                    sources_in_build_files)
+
 NEW = ["rna_frontiers_build", "rna_frontiers_info_get", "rna_frontiers_download", "rna_frontiers_device_ptr"]
 RNA_EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import _build
-    _build.native()
-    from ros_navigation_amd import capi
-    return capi
 
 
 def test_new_symbols_are_exported_and_bound(capi):
@@ -42,16 +29,11 @@ def test_new_symbols_are_exported_and_bound(capi):
 def test_struct_layouts_abi_version_and_profile_slots(capi, tmp_path):
     rec = ("label", "size", "min_i", "max_i", "min_j", "max_j", "nearest", "cost", "sum_i", "sum_j")
     info = ("cells", "clusters_all", "clusters", "largest", "min_size", "ranked", "stale", "reserved")
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "rna.h"\nint main(void) {\n'
+    got = c_values(tmp_path,
                    '  printf("%zu %zu %d %d %d\\n", sizeof(rna_frontier), sizeof(rna_frontier_info), RNA_FRONTIER_RANK, RNA_ABI_VERSION,'
                    ' (int)RNA_K_COUNT);\n'
                    + "".join('  printf("%%zu ", offsetof(rna_frontier, %s));\n' % f for f in rec)
-                   + "".join('  printf("%%zu ", offsetof(rna_frontier_info, %s));\n' % f for f in info)
-                   + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-I" + INCLUDE, str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+                   + "".join('  printf("%%zu ", offsetof(rna_frontier_info, %s));\n' % f for f in info))
     F, D, I, DI = capi.Frontier, capi.FRONTIER_DTYPE, capi.FrontierInfo, capi.FRONTIER_INFO_DTYPE
     assert got[0] == C.sizeof(F) == D.itemsize == 48 and got[1] == C.sizeof(I) == DI.itemsize == 32
     assert got[2] == capi.FRONTIER_RANK == 1
@@ -90,24 +72,11 @@ def test_argument_checks_that_need_no_device(capi):
     assert L.rna_frontiers_device_ptr(None) is None
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@needs_hipcc
 def test_kernel_budget():
     """frontier.hip cross-compiles for gfx950; no kernel uses scratch, and static LDS stays at or below 40 KiB per workgroup:
     four tiles per compute unit (the classify kernel holds a 64 x 64 int32 parent tile, 16 KiB, plus its bit rows)"""
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-c",
-                          os.path.join(CSRC, "frontier.hip"), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-        for key in ("VGPRs", r"LDS Size \[bytes/block\]", r"ScratchSize \[bytes/lane\]"):
-            m = re.search(r"remark:\s+" + key + r": (\d+)", line)
-            if m and name:
-                res[name][key.split(" ")[0]] = int(m.group(1))
+    res = resources("frontier.hip")
     want = {"fr_classify_kernel", "fr_seam_kernel", "fr_flatten_kernel", "fr_init_kernel", "fr_stats_kernel", "fr_compact_kernel"}
     assert len(res) == len(want) and all(any(w in k for k in res) for w in want), list(res)
     for k, v in res.items():
@@ -117,8 +86,7 @@ def test_kernel_budget():
 
 
 def test_sources_are_in_both_build_files():
-    assert re.search(r"^SRCS\s*:=.*\bfrontier\.hip\b", open(os.path.join(CSRC, "Makefile")).read(), re.M)
-    assert re.search(r"set\(RNA_SRCS[^)]*\bfrontier\b", open(os.path.join(ROOT, "CMakeLists.txt")).read())
+    sources_in_build_files("frontier")
 
 
 def test_cpp_additions_compile_and_link(capi, tmp_path):

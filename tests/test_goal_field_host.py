@@ -2,28 +2,15 @@
 bound, the info struct and the two sentinels agree between the header, a compiled C snippet and the Python mirror, argument
 checks that need no device, the C++ host class compiles and links, and the kernels' resource budget on gfx950."""
 import ctypes as C
-import os
-import re
 import subprocess
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ros_navigation_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
-HIPCC = "/opt/rocm/bin/hipcc"
+from _build import HPP, LIB_DIR, c_values, capi, needs_hipcc, resources  # noqa: F401  (capi: the fixture)
+
 NEW = ["rna_goal_field_build", "rna_goal_field_info_get", "rna_goal_field_download", "rna_goal_field_device_ptr",
        "rna_goal_field_paths", "rna_goal_field_paths_device"]
 RNA_EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import _build
-    _build.native()
-    from ros_navigation_amd import capi
-    return capi
 
 
 def test_new_symbols_are_exported_and_bound(capi):
@@ -37,22 +24,11 @@ def test_new_symbols_are_exported_and_bound(capi):
 
 
 def test_info_struct_and_sentinels_match_the_header(capi, tmp_path):
-    src = tmp_path / "layout.c"
-    src.write_text(r'''
-#include <stddef.h>
-#include <stdio.h>
-#include "rna.h"
-int main(void) {
+    got = c_values(tmp_path, r'''
   printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %d %d %d\n", sizeof(rna_goal_field_info), offsetof(rna_goal_field_info, goal),
          offsetof(rna_goal_field_info, status), offsetof(rna_goal_field_info, reached), offsetof(rna_goal_field_info, max_cost),
          offsetof(rna_goal_field_info, rounds), offsetof(rna_goal_field_info, tile_jobs), offsetof(rna_goal_field_info, tiles_reached),
-         offsetof(rna_goal_field_info, stale), RNA_GOAL_FIELD_UNREACHED, RNA_GOAL_FIELD_FAR, RNA_ABI_VERSION);
-  return 0;
-}
-''')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-I" + INCLUDE, str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+         offsetof(rna_goal_field_info, stale), RNA_GOAL_FIELD_UNREACHED, RNA_GOAL_FIELD_FAR, RNA_ABI_VERSION);''')
     dt = capi.GOAL_FIELD_INFO_DTYPE
     names = ("goal", "status", "reached", "max_cost", "rounds", "tile_jobs", "tiles_reached", "stale")
     assert dt.names == names
@@ -101,33 +77,19 @@ int main(int argc, char**) {
   }
   return 0;
 }
-''' % os.path.join(ROOT, "ros_navigation_amd", "host", "move_control_amd.hpp"))
-    lib_dir = os.path.join(ROOT, "ros_navigation_amd")
-    subprocess.check_call(["g++", "-std=c++11", "-Wall", str(src), "-o", str(tmp_path / "goal_field_host"), "-L" + lib_dir, "-lrna",
-                           "-Wl,-rpath," + lib_dir, "-lpthread"])
+''' % HPP)
+    subprocess.check_call(["g++", "-std=c++11", "-Wall", str(src), "-o", str(tmp_path / "goal_field_host"), "-L" + LIB_DIR, "-lrna",
+                           "-Wl,-rpath," + LIB_DIR, "-lpthread"])
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@needs_hipcc
 def test_goal_field_kernel_budget():
     """Every kernel of goal_field.hip compiles for gfx950 without scratch.  Budget of the relaxation kernel (one 256-thread
     workgroup per 64 x 64 tile): the tile's field with a one-cell halo (66 rows of 67 words, 17.3 KiB), its mask bytes in
     both lane layouts (2 x 4 KiB) and a few words must leave room for at least 4 workgroups per CU -- a round holds a few
     hundred tile jobs whose sweeps wait on LDS round trips, so it is other workgroups on the CU that hide them: LDS <= 40 KiB
     (4 x 40 = the CU's 160 KiB) and VGPRs <= 128 (4 wavefronts per SIMD of 512 registers per lane)."""
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-c",
-                          os.path.join(CSRC, "goal_field.hip"), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-        for key in ("VGPRs", r"LDS Size \[bytes/block\]", r"ScratchSize \[bytes/lane\]"):
-            m = re.search(r"remark:\s+" + key + r": (\d+)", line)
-            if m and name:
-                res[name][key.split(" ")[0]] = int(m.group(1))
+    res = resources("goal_field.hip")
     kernels = {k: next(v for n, v in res.items() if k in n) for k in
                ("gf_init_kernel", "gf_seed_kernel", "gf_round_kernel", "gf_finalize_kernel", "gf_paths_kernel")}
     for k, v in kernels.items():

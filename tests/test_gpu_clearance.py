@@ -16,40 +16,12 @@ import numpy as np
 import pytest
 
 import _oracle as O
+from _gpu import (NB_DI, NB_DJ, NB_W, NONE, TABLE, UNREACHED, Hip, R, engine_centre, make_engine, to_buffer,  # noqa: F401  (R: the fixture)
+                  to_map)
 
 pytestmark = pytest.mark.gpu
 
-NONE = 0xFFFF
-UNREACHED = 0x7fffffff
-NB_DI = (-1, 0, 1, -1, 1, -1, 0, 1)
-NB_DJ = (-1, -1, -1, 0, 0, 1, 1, 1)
-NB_W = (1414, 1000, 1414, 1000, 1000, 1414, 1000, 1414)
 RES = 0.05
-TABLE = np.array([0, 5000, 4000, 3000, 2000, 1200, 600, 300], np.uint16)   # R = 7
-
-
-@pytest.fixture(scope="module")
-def R():
-    import ros_navigation_amd as R
-    R.capi.lib()
-    return R
-
-
-def make(R, rows, cols, master=None, pos=(0.0, 0.0)):
-    e = R.Engine(rows * RES, cols * RES, RES, *pos)
-    assert (e.rows, e.cols) == (rows, cols)
-    if master is not None:
-        e.upload(R.capi.LAYER_MASTER, master)
-    return e
-
-
-def to_map(a, rows, cols, s0, s1):
-    """buffer order -> map order, as a [j, i] array"""
-    return np.roll(np.roll(a.reshape(cols, rows), -s1, axis=0), -s0, axis=1)
-
-
-def to_buffer(a, rows, cols, s0, s1):
-    return np.ascontiguousarray(np.roll(np.roll(a.reshape(cols, rows), s1, axis=0), s0, axis=1).reshape(-1))
 
 
 # ---- the clearance oracle ----
@@ -147,7 +119,7 @@ def shape_for(cap):
 @pytest.mark.parametrize("cap", [1, 7, 20, 63])
 def test_clearance_matches_the_oracle(R, cap):
     rows, cols = shape_for(cap)
-    e = make(R, rows, cols)
+    e = make_engine(R, rows, cols)
     assert e.clearance_info() == (0, False) and e.clearance_ptr() is None
     buf = np.zeros(rows * cols, np.uint16)
     assert e._L.rna_clearance_download(e.h, buf.ctypes.data, buf.size) == -5          # RNA_ESTATE before a build
@@ -170,7 +142,7 @@ def test_clearance_matches_the_oracle(R, cap):
 def test_clearance_uses_the_robot_radius(R):
     rows, cols = 130, 70
     master = obstacle_map(rows, cols, 7, 77)
-    e = make(R, rows, cols, master)
+    e = make_engine(R, rows, cols, master)
     plain = check_clearance(e, 7)
     n_plain = int(e.astar_blocked_mask().sum())
     e.astar_robot_radius(0.15)
@@ -186,7 +158,7 @@ def test_clearance_uses_the_robot_radius(R):
 # ---- 3. a moved map: an obstacle and its neighbourhood across the buffer seam ----
 def test_clearance_on_a_moved_map(R):
     rows, cols = 130, 70
-    e = make(R, rows, cols, np.zeros(rows * cols, np.float32), pos=(1.25, -2.5))
+    e = make_engine(R, rows, cols, np.zeros(rows * cols, np.float32), pos=(1.25, -2.5))
     assert e.move(1.25 + 37 * RES, -2.5 - 22 * RES)
     g = e.geometry()
     s0, s1 = g.start_index[0], g.start_index[1]
@@ -206,24 +178,20 @@ def test_clearance_on_a_moved_map(R):
 
 
 # ---- 4. stale after a HIMM batch, a rebuild equals a fresh engine's ----
-def centre(e, lin):
-    return e.get_position(lin % e.rows, lin // e.rows)
-
-
 def test_clearance_stale_after_a_map_update_and_rebuild(R):
     rows, cols = 130, 70
     m = np.zeros((cols, rows), np.float32)
     m[0, :] = m[-1, :] = m[:, 0] = m[:, -1] = 180.0
     master = m.reshape(-1)
-    e = make(R, rows, cols, master)
+    e = make_engine(R, rows, cols, master)
     e.upload(R.capi.LAYER_LASER, master)
     e.compose_master(1)
     old = check_clearance(e, 20)
     assert old[35, 65] == NONE
     cell = 65 + 35 * rows
     rs = np.zeros(1, R.capi.RAY_DTYPE)
-    rs["sx"][0], rs["sy"][0] = centre(e, cell + 6 * rows)
-    rs["ex"][0], rs["ey"][0] = centre(e, cell)
+    rs["sx"][0], rs["sy"][0] = engine_centre(e, cell + 6 * rows)
+    rs["ex"][0], rs["ey"][0] = engine_centre(e, cell)
     e.update_map(rs, compose_mode=0)
     assert e.clearance_info() == (20, True)
     assert np.array_equal(to_map(e.clearance_download(), rows, cols, 0, 0), old)      # a snapshot until it is rebuilt
@@ -231,7 +199,7 @@ def test_clearance_stale_after_a_map_update_and_rebuild(R):
     assert now[cell] > 0
     new = check_clearance(e, 20)
     assert new[35, 65] == 0 and new[35, 60] == 25 and not np.array_equal(new, old)
-    fresh = make(R, rows, cols, now)
+    fresh = make_engine(R, rows, cols, now)
     assert np.array_equal(fresh.clearance(20), e.clearance_download())
     fresh.close()
     e.close()
@@ -359,7 +327,7 @@ def test_field_with_a_clearance_cost(R, seed):
     m = obstacle_map(rows, cols, 7, 100 + seed, rects=4 + 3 * seed)
     m[63:66, 63:66] = 0.0                                   # the goal on the tile corner (64, 64) and its ring are free
     m[62, 64] = 180.0                                       # ... two cells from an obstacle
-    e = make(R, rows, cols, m)
+    e = make_engine(R, rows, cols, m)
     e.goal_field_clearance_cost(TABLE)
     assert np.array_equal(e.goal_field_clearance_cost(), TABLE)
     rng = np.random.default_rng(seed)
@@ -384,7 +352,7 @@ def test_field_with_a_clearance_cost(R, seed):
 # ---- 6. an all-zero table is the table-free build, byte for byte ----
 def test_zero_table_equals_the_plain_field(R):
     rows, cols = 130, 70
-    e = make(R, rows, cols, obstacle_map(rows, cols, 7, 61, rects=12))
+    e = make_engine(R, rows, cols, obstacle_map(rows, cols, 7, 61, rects=12))
     goal = int(np.flatnonzero(e.astar_blocked_mask() == 0)[777])
     plain_info = e.goal_field(goal)
     plain = e.goal_field_download(want_next=True)
@@ -411,7 +379,7 @@ def test_penalised_path_keeps_its_distance(R):
     m = np.zeros((cols, rows), np.float32)
     m[0, :] = m[-1, :] = m[:, 0] = m[:, -1] = 180.0
     m[35, 0:100] = 180.0                                     # a wall along j = 35 with its tip at i = 99: the way round is a U-turn
-    e = make(R, rows, cols, m)
+    e = make_engine(R, rows, cols, m)
     start, goal = 10 + 30 * rows, 10 + 40 * rows
     e.goal_field(goal)
     paths, res = e.goal_field_paths(np.array([start], np.int32), 1024)
@@ -436,7 +404,7 @@ def test_penalised_path_keeps_its_distance(R):
 # ---- 8. setting the table marks the field stale; clearing it and rebuilding gives the plain field ----
 def test_table_changes_mark_the_field_stale(R):
     rows, cols = 130, 70
-    e = make(R, rows, cols, obstacle_map(rows, cols, 7, 88, rects=10))
+    e = make_engine(R, rows, cols, obstacle_map(rows, cols, 7, 88, rects=10))
     goal = int(np.flatnonzero(e.astar_blocked_mask() == 0)[1234])
     assert len(e.goal_field_clearance_cost()) == 0
     e.goal_field_clearance_cost(TABLE)                       # (before any field: nothing to mark)
@@ -463,35 +431,11 @@ def test_table_changes_mark_the_field_stale(R):
 
 
 # ---- 9. with one pipelined batch in flight ----
-class _Hip:
-    def __init__(self):
-        self.h = C.CDLL("libamdhip64.so")
-        self.h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.h.hipFree.argtypes = [C.c_void_p]
-
-    def alloc(self, nbytes):
-        p = C.c_void_p()
-        assert self.h.hipMalloc(C.byref(p), nbytes) == 0
-        return p.value
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        p = self.alloc(a.nbytes)
-        assert self.h.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0
-        return p
-
-    def download(self, p, dtype, count):
-        out = np.empty(count, dtype)
-        assert self.h.hipMemcpy(out.ctypes.data, p, out.nbytes, 2) == 0
-        return out
-
-
 def test_coexists_with_a_pipelined_batch(R):
-    hip = _Hip()
+    hip = Hip()
     rows, cols = 192, 160
     master = R.synth.obstacles_rect(rows, cols, density=0.2, seed=2)
-    e = make(R, rows, cols, master)
+    e = make_engine(R, rows, cols, master)
     blocked, nbr = O.astar_masks(master, rows, cols)
     e.astar_pipeline_depth(4)
     e.astar_configure(max_queries=32)
@@ -518,7 +462,7 @@ def test_coexists_with_a_pipelined_batch(R):
 # ---- 10. a clone carries the table (not the fields) ----
 def test_clone_and_submap_carry_the_table(R):
     rows, cols = 130, 70
-    e = make(R, rows, cols, obstacle_map(rows, cols, 7, 9, rects=8))
+    e = make_engine(R, rows, cols, obstacle_map(rows, cols, 7, 9, rects=8))
     e.goal_field_clearance_cost(TABLE)
     goal = int(np.flatnonzero(e.astar_blocked_mask() == 0)[900])
     e.goal_field(goal)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import _oracle as O
+from _gpu import Hip, R, centre, make_engine_and_geom, map_nbr  # noqa: F401  (R: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -16,21 +17,8 @@ REFERENCE = O.ref_gridmap() is not None
 _discs = {}
 
 
-@pytest.fixture(scope="module")
-def R():
-    import ros_navigation_amd as R
-    R.capi.lib()
-    return R
-
-
 def geom_key(g):
     return (tuple(g.len), tuple(g.pos), g.res, tuple(g.size), tuple(g.start))
-
-
-def centre(g, bi, bj):
-    p = O.d2(0.0, 0.0)
-    O.lib().og_position_from_index(C.byref(g), O.i2(bi, bj), p)
-    return p[0], p[1]
 
 
 def disc_lists(g, r):
@@ -40,7 +28,7 @@ def disc_lists(g, r):
         rows, cols = g.size[0], g.size[1]
         offs, idx = [0], []
         for lin in range(rows * cols):
-            c = O.circle_cells(g, centre(g, lin % rows, lin // rows), r, reference=REFERENCE)
+            c = O.circle_cells(g, centre(g, lin), r, reference=REFERENCE)
             ok = (c[:, 0] >= 0) & (c[:, 0] < rows) & (c[:, 1] >= 0) & (c[:, 1] < cols)
             idx.append(c[ok, 0] + c[ok, 1] * rows)
             offs.append(offs[-1] + int(ok.sum()))
@@ -53,17 +41,6 @@ def ref_blocked(g, master, r):
     offs, idx = disc_lists(g, r)
     hit = np.concatenate([[0], np.cumsum(occ[idx])])
     return (hit[offs[1:]] - hit[offs[:-1]] > 0).astype(np.uint8)
-
-
-def map_nbr(g, blocked):
-    """og_astar_nbr_mask of a blocked set, taken in MAP space (a moved map's neighbours wrap round the buffer, not the edge)"""
-    rows, cols, s0, s1 = g.size[0], g.size[1], g.start[0], g.start[1]
-    b = np.roll(np.roll(blocked.reshape(cols, rows), -s1, axis=0), -s0, axis=1)
-    nbr = np.zeros(rows * cols, np.uint8)
-    u8 = C.POINTER(C.c_uint8)
-    b = np.ascontiguousarray(b.reshape(-1))
-    O.lib().og_astar_nbr_mask(b.ctypes.data_as(u8), rows, cols, nbr.ctypes.data_as(u8))
-    return np.roll(np.roll(nbr.reshape(cols, rows), s1, axis=0), s0, axis=1).reshape(-1)
 
 
 def sample_map(rows, cols, seed, occupied=0.004, edge=True):
@@ -82,14 +59,6 @@ def sample_map(rows, cols, seed, occupied=0.004, edge=True):
         m[rng.integers(0, cols), -1] = 50.0
         m[-1, -1] = 7.0
     return m.reshape(-1)
-
-
-def make(R, rows, cols, pos, master, res=0.05):
-    e = R.Engine(rows * res, cols * res, res, *pos)
-    g = O.make_geom(rows * res, cols * res, res, *pos)
-    assert (e.rows, e.cols) == (rows, cols) == (g.size[0], g.size[1])
-    e.upload(R.capi.LAYER_MASTER, master)
-    return e, g
 
 
 def move_both(R, e, g, master, target):
@@ -122,7 +91,7 @@ CASES = [  # rows, cols, position, radii
 @pytest.mark.parametrize("rows,cols,pos,radii", CASES)
 def test_blocked_set_matches_reference_predicate(R, rows, cols, pos, radii):
     master = sample_map(rows, cols, seed=rows + cols)
-    e, g = make(R, rows, cols, pos, master)
+    e, g = make_engine_and_geom(R, rows, cols, master, pos)
     for r in radii:
         assert e.astar_robot_radius(r) == r
         check_masks(e, g, master, r)
@@ -132,7 +101,7 @@ def test_blocked_set_matches_reference_predicate(R, rows, cols, pos, radii):
 def test_blocked_set_on_a_moved_map(R):
     rows, cols = 96, 80
     master = sample_map(rows, cols, seed=5)
-    e, g = make(R, rows, cols, (1.25, -2.5), master)
+    e, g = make_engine_and_geom(R, rows, cols, master, (1.25, -2.5))
     e.astar_robot_radius(0.3)
     check_masks(e, g, master, 0.3)
     ref = move_both(R, e, g, master, (2.33, -1.61))
@@ -177,7 +146,7 @@ def queries(rng, blocked, n, want_band):
                                                    (257, 131, (1.25, -2.5), 0.3, True)])
 def test_search_matches_oracle(R, rows, cols, pos, r, moved):
     master = sample_map(rows, cols, seed=7 + rows, occupied=0.002)
-    e, g = make(R, rows, cols, pos, master)
+    e, g = make_engine_and_geom(R, rows, cols, master, pos)
     if moved:
         master = move_both(R, e, g, master, (pos[0] + 3.37, pos[1] - 1.12))
     e.astar_robot_radius(r)
@@ -191,30 +160,6 @@ def test_search_matches_oracle(R, rows, cols, pos, r, moved):
     assert found >= 32
     assert (res["status"][:16] != 0).all()          # a start or goal inside the inflated band answers as a blocked one
     e.close()
-
-
-class _Hip:
-    def __init__(self):
-        self.h = C.CDLL("libamdhip64.so")
-        self.h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.h.hipFree.argtypes = [C.c_void_p]
-
-    def alloc(self, nbytes):
-        p = C.c_void_p()
-        assert self.h.hipMalloc(C.byref(p), nbytes) == 0
-        return p.value
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        p = self.alloc(a.nbytes)
-        assert self.h.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0
-        return p
-
-    def download(self, p, dtype, count):
-        out = np.empty(count, dtype)
-        assert self.h.hipMemcpy(out.ctypes.data, p, out.nbytes, 2) == 0
-        return out
 
 
 def rays(rng, n, half, cx=0.0, cy=0.0, hit=0.7):
@@ -232,10 +177,10 @@ def test_pipelined_batches_keep_their_snapshot_across_updates_and_radius_changes
     after the fourth: every batch answers for the map AND the radius of its launch.  (Few marking rays and a second radius
     of 0.25 m keep the free space connected: 44-64 of the 64 queries of each batch have a path, and 39-60 of them answer
     differently under the other radius.)"""
-    hip = _Hip()
+    hip = Hip()
     rows = cols = 128
     master = sample_map(rows, cols, seed=11, occupied=0.002, edge=False)
-    e, g = make(R, rows, cols, (0.0, 0.0), master)
+    e, g = make_engine_and_geom(R, rows, cols, master, (0.0, 0.0))
     e.upload(R.capi.LAYER_LASER, master)
     e.compose_master(1)
     e.astar_robot_radius(0.15)
@@ -270,7 +215,7 @@ def test_pipelined_batches_keep_their_snapshot_across_updates_and_radius_changes
 def test_incremental_refresh_equals_full_rebuild(R):
     rows, cols = 200, 150
     master = sample_map(rows, cols, seed=3, occupied=0.002)
-    e, g = make(R, rows, cols, (0.4, -0.3), master)
+    e, g = make_engine_and_geom(R, rows, cols, master, (0.4, -0.3))
     e.upload(R.capi.LAYER_LASER, master)
     e.compose_master(1)
     e.astar_robot_radius(0.3)
@@ -292,7 +237,7 @@ def test_incremental_refresh_equals_full_rebuild(R):
 def test_if_blocked_matches_reference_predicate(R):
     rows, cols, pos, res = 96, 80, (1.25, -2.5), 0.05
     master = sample_map(rows, cols, seed=21)
-    e, g = make(R, rows, cols, pos, master)
+    e, g = make_engine_and_geom(R, rows, cols, master, pos)
     occ = (~np.isnan(master)) & (master > 0)
     rng = np.random.default_rng(4)
     L = np.array([rows * res, cols * res])

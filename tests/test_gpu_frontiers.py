@@ -14,20 +14,13 @@ import numpy as np
 import pytest
 
 import _oracle as O
-from test_gpu_clearance import RES, TABLE, _Hip, centre, make, to_buffer, to_map
+from _gpu import TABLE, UNREACHED, Hip, R, engine_centre, make_engine, to_buffer, to_map  # noqa: F401  (R: the fixture)
 
 pytestmark = pytest.mark.gpu
 
-UNREACHED = 0x7fffffff
+RES = 0.05
 RNA_ECAPACITY, RNA_ESTATE = -4, -5
 NAN = np.float32(np.nan)
-
-
-@pytest.fixture(scope="module")
-def R():
-    import ros_navigation_amd as R
-    R.capi.lib()
-    return R
 
 
 # ---- the map generators ([j, i] arrays) ----
@@ -152,7 +145,7 @@ def scipy_count():
 @pytest.mark.parametrize("seed", range(6))
 def test_explored_map(R, seed, scipy_count):
     rows, cols = 130, 70
-    e = make(R, rows, cols)
+    e = make_engine(R, rows, cols)
     L, h = e._L, e.h
     # before any build
     lab = np.zeros(rows * cols, np.int32)
@@ -198,7 +191,7 @@ def test_explored_map(R, seed, scipy_count):
 # ---- 2. one long component through every tile ----
 def test_serpentine(R):
     rows, cols = 200, 136
-    e = make(R, rows, cols, serpentine(rows, cols).reshape(-1))
+    e = make_engine(R, rows, cols, serpentine(rows, cols).reshape(-1))
     w, recs = check(e, R)
     assert len(w.clusters) == 1 and len(w.tiles_of(w.clusters[0])) == 12
     r = recs[0]
@@ -212,7 +205,7 @@ def test_serpentine(R):
 # ---- 3. degenerate maps ----
 def test_degenerate_maps(R):
     rows, cols = 130, 70
-    e = make(R, rows, cols)
+    e = make_engine(R, rows, cols)
 
     def run(m):
         e.upload(R.capi.LAYER_MASTER, m.reshape(-1))
@@ -253,7 +246,7 @@ def test_degenerate_maps(R):
 # ---- 4. robot radius: frontier cells inside the inflated set disappear ----
 def test_robot_radius(R):
     rows, cols = 130, 70
-    e = make(R, rows, cols, explored_map(rows, cols, 3).reshape(-1))
+    e = make_engine(R, rows, cols, explored_map(rows, cols, 3).reshape(-1))
     w0, _ = check(e, R)
     e.astar_robot_radius(0.15)
     assert e.frontiers_info()["stale"] == 1
@@ -268,7 +261,7 @@ def test_robot_radius(R):
 # ---- 5. a moved map: clusters across both buffer seams, buffer neighbours that are no map neighbours ----
 def test_moved_map(R):
     rows, cols = 130, 70
-    e = make(R, rows, cols, np.zeros(rows * cols, np.float32), pos=(1.25, -2.5))
+    e = make_engine(R, rows, cols, np.zeros(rows * cols, np.float32), pos=(1.25, -2.5))
     assert e.move(1.25 + 37 * RES, -2.5 - 22 * RES)
     g = e.geometry()
     s0, s1 = g.start_index[0], g.start_index[1]
@@ -316,7 +309,7 @@ def room_map(rows, cols):
 @pytest.mark.parametrize("table", [None, TABLE])
 def test_ranking(R, table):
     rows, cols = 130, 70
-    e = make(R, rows, cols, room_map(rows, cols).reshape(-1))
+    e = make_engine(R, rows, cols, room_map(rows, cols).reshape(-1))
     if table is not None:
         e.goal_field_clearance_cost(table)
     with pytest.raises(R.capi.RnaError, match="RNA_ESTATE"):
@@ -355,13 +348,13 @@ def test_snapshot_and_stale(R):
     m[20:50, 20:70] = 0.0
     m[30:33, 40:44] = 180.0
     master = m.reshape(-1)
-    e = make(R, rows, cols, master)
+    e = make_engine(R, rows, cols, master)
     e.upload(R.capi.LAYER_LASER, master)
     e.compose_master(1)
     old, _ = check(e, R)
     rs = np.zeros(1, R.capi.RAY_DTYPE)
-    rs["sx"][0], rs["sy"][0] = centre(e, 60 + 35 * rows)                     # from the known space out into the unknown
-    rs["ex"][0], rs["ey"][0] = centre(e, 90 + 35 * rows)
+    rs["sx"][0], rs["sy"][0] = engine_centre(e, 60 + 35 * rows)                     # from the known space out into the unknown
+    rs["ex"][0], rs["ey"][0] = engine_centre(e, 90 + 35 * rows)
     e.update_map(rs, compose_mode=0)
     assert e.frontiers_info()["stale"] == 1
     assert np.array_equal(e.frontier_labels(), old.labels)                    # unchanged until a rebuild
@@ -369,7 +362,7 @@ def test_snapshot_and_stale(R):
     assert np.isnan(now).sum() < np.isnan(master).sum()                      # the ray made unknown cells known
     new, _ = check(e, R)
     assert e.frontiers_info()["stale"] == 0 and not np.array_equal(new.labels, old.labels)
-    fresh = make(R, rows, cols, now)
+    fresh = make_engine(R, rows, cols, now)
     frecs, finfo = fresh.frontiers()
     recs, info = e.frontiers()
     assert np.array_equal(fresh.frontier_labels(), e.frontier_labels()) and frecs.tobytes() == recs.tobytes() and finfo == info
@@ -379,14 +372,14 @@ def test_snapshot_and_stale(R):
 
 # ---- 8. with one pipelined batch in flight ----
 def test_coexists_with_a_pipelined_batch(R):
-    hip = _Hip()
+    hip = Hip()
     rows, cols = 192, 160
     m = R.synth.obstacles_rect(rows, cols, density=0.2, seed=2).reshape(cols, rows).copy()
     m[:, 150:] = np.nan
     m[130:, :] = np.nan
     m[60:70, 60:70] = np.nan
     master = np.ascontiguousarray(m.reshape(-1))
-    e = make(R, rows, cols, master)
+    e = make_engine(R, rows, cols, master)
     blocked, nbr = O.astar_masks(master, rows, cols)
     e.astar_pipeline_depth(4)
     e.astar_configure(max_queries=32)
@@ -411,7 +404,7 @@ def test_coexists_with_a_pipelined_batch(R):
 # ---- clones and submaps copy nothing of it ----
 def test_clone_and_submap_copy_nothing(R):
     rows, cols = 130, 70
-    e = make(R, rows, cols, explored_map(rows, cols, 4).reshape(-1))
+    e = make_engine(R, rows, cols, explored_map(rows, cols, 4).reshape(-1))
     e.frontiers()
     zero = dict.fromkeys(R.capi.FRONTIER_INFO_DTYPE.names, 0)
     h = C.c_void_p()

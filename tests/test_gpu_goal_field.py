@@ -11,43 +11,13 @@ import numpy as np
 import pytest
 
 import _oracle as O
+from _gpu import (NB_DI, NB_DJ, UNREACHED, Hip, R, blocked_of, centre, make_engine_and_geom, map_nbr,  # noqa: F401  (R: the fixture)
+                  to_buffer, to_map)
 
 pytestmark = pytest.mark.gpu
 
-UNREACHED, FAR = 0x7fffffff, 0x7ffffffe
-NB_DI = (-1, 0, 1, -1, 1, -1, 0, 1)
-NB_DJ = (-1, -1, -1, 0, 0, 1, 1, 1)
+FAR = 0x7ffffffe
 RES = 0.05
-
-
-@pytest.fixture(scope="module")
-def R():
-    import ros_navigation_amd as R
-    R.capi.lib()
-    return R
-
-
-def make(R, rows, cols, master, pos=(0.0, 0.0)):
-    e = R.Engine(rows * RES, cols * RES, RES, *pos)
-    g = O.make_geom(rows * RES, cols * RES, RES, *pos)
-    assert (e.rows, e.cols) == (rows, cols) == (g.size[0], g.size[1])
-    e.upload(R.capi.LAYER_MASTER, master)
-    return e, g
-
-
-def blocked_of(master):
-    return ((~np.isnan(master)) & (master > 0)).astype(np.uint8)
-
-
-def map_nbr(g, blocked):
-    """og_astar_nbr_mask of a blocked set, taken in MAP space (a moved map's neighbours wrap round the buffer, not the edge)"""
-    rows, cols, s0, s1 = g.size[0], g.size[1], g.start[0], g.start[1]
-    b = np.roll(np.roll(blocked.reshape(cols, rows), -s1, axis=0), -s0, axis=1)
-    nbr = np.zeros(rows * cols, np.uint8)
-    u8 = C.POINTER(C.c_uint8)
-    b = np.ascontiguousarray(b.reshape(-1))
-    O.lib().og_astar_nbr_mask(b.ctypes.data_as(u8), rows, cols, nbr.ctypes.data_as(u8))
-    return np.roll(np.roll(nbr.reshape(cols, rows), s1, axis=0), s0, axis=1).reshape(-1)
 
 
 def add_pocket(master, rows, cols, i0, j0):
@@ -128,7 +98,7 @@ def maps_for(R, rows, cols, kind):
 def test_field_parity(R, rows, cols, kind):
     master = maps_for(R, rows, cols, kind).copy()
     pocket = add_pocket(master, rows, cols, rows // 3, cols // 2)
-    e, g = make(R, rows, cols, master)
+    e, g = make_engine_and_geom(R, rows, cols, master)
     blocked, nbr = O.astar_masks(master, rows, cols)
     assert np.array_equal(e.nbr_mask(), nbr)
     comp = np.flatnonzero(R.synth.free_component(master, rows, cols))
@@ -148,7 +118,7 @@ def test_field_parity(R, rows, cols, kind):
 
 def test_empty_map_is_octile_distance(R):
     rows, cols = 200, 333
-    e, g = make(R, rows, cols, np.full(rows * cols, np.nan, np.float32))
+    e, g = make_engine_and_geom(R, rows, cols, np.full(rows * cols, np.nan, np.float32))
     goal = 77 + 150 * rows
     info = e.goal_field(goal)
     i, j = np.meshgrid(np.arange(rows), np.arange(cols))          # [j, i]
@@ -173,7 +143,7 @@ def paths_case(R, rows=192, cols=160, density=0.3, seed=5):
 def test_paths_match_reversed_oracle_paths(R):
     rows, cols = 192, 160
     master, blocked, nbr, goal, starts = paths_case(R)
-    e, g = make(R, rows, cols, master)
+    e, g = make_engine_and_geom(R, rows, cols, master)
     info = e.goal_field(goal)
     assert 2 * info["reached"] >= int((blocked == 0).sum())
     ref = lambda s: ref_path(nbr, rows, cols, goal, s)   # noqa: E731
@@ -202,7 +172,7 @@ def test_agrees_with_the_batch_search(R):
     rows, cols = 192, 160
     master, blocked, nbr, goal, starts = paths_case(R, seed=8)
     starts = starts[:257]
-    e, g = make(R, rows, cols, master)
+    e, g = make_engine_and_geom(R, rows, cols, master)
     e.goal_field(goal)
     paths, results = e.goal_field_paths(starts, 4096)
     q = np.zeros(len(starts), R.capi.ASTAR_QUERY_DTYPE)
@@ -219,7 +189,7 @@ def test_agrees_with_the_batch_search(R):
 def test_robot_radius(R):
     rows = cols = 256
     master = R.synth.obstacles_rect(rows, cols, density=0.1, seed=4)
-    e, g = make(R, rows, cols, master)
+    e, g = make_engine_and_geom(R, rows, cols, master)
     e.astar_robot_radius(0.3)
     nbr, blocked = e.nbr_mask(), e.astar_blocked_mask()
     assert blocked.sum() > blocked_of(master).sum()
@@ -243,7 +213,7 @@ def test_moved_map(R):
     master = R.synth.obstacles_rect(rows, cols, density=0.2, seed=6).copy()
     m = master.reshape(cols, rows)
     m[0, :] = m[-1, :] = m[:, 0] = m[:, -1] = 0.0     # no border wall: it would lie along the buffer seam after the move
-    e, g = make(R, rows, cols, master, pos=(1.25, -2.5))
+    e, g = make_engine_and_geom(R, rows, cols, master, pos=(1.25, -2.5))
     ref = master.copy()
     ptrs = (C.POINTER(C.c_float) * 1)(O.fptr(ref))
     regs = (O.Region * 4)()
@@ -257,19 +227,19 @@ def test_moved_map(R):
     nbr = map_nbr(g, blocked)
     assert np.array_equal(e.nbr_mask(), nbr)
 
-    def to_map(a):     # buffer order -> map order
-        return np.ascontiguousarray(np.roll(np.roll(a.reshape(cols, rows), -s1, axis=0), -s0, axis=1).reshape(-1))
+    def flat_map(a):     # buffer order -> map order, flat
+        return np.ascontiguousarray(to_map(a, rows, cols, s0, s1).reshape(-1))
 
     def lin_to_map(c):
         return (c % rows - s0) % rows + ((c // rows - s1) % cols) * rows
 
-    comp = np.flatnonzero(R.synth.free_component(to_map(ref), rows, cols))       # map-space cells
+    comp = np.flatnonzero(R.synth.free_component(flat_map(ref), rows, cols))       # map-space cells
     comp = (comp % rows + s0) % rows + ((comp // rows + s1) % cols) * rows        # -> buffer cells
     rng = np.random.default_rng(3)
     goal = int(rng.choice(comp))
     info = e.goal_field(goal)
-    field_map, res = ref_field(to_map(nbr), rows, cols, lin_to_map(goal), to_map(blocked))
-    field_ref = np.roll(np.roll(field_map.reshape(cols, rows), s1, axis=0), s0, axis=1).reshape(-1)
+    field_map, res = ref_field(flat_map(nbr), rows, cols, lin_to_map(goal), flat_map(blocked))
+    field_ref = to_buffer(field_map, rows, cols, s0, s1)
     check_field(e, info, field_ref, res)
     assert 2 * info["reached"] >= int((blocked == 0).sum())
     starts = rng.choice(comp, 64).astype(np.int32)
@@ -292,12 +262,6 @@ def test_moved_map(R):
     e.close()
 
 
-def centre(g, lin):
-    p = O.d2(0.0, 0.0)
-    O.lib().og_position_from_index(C.byref(g), O.i2(lin % g.size[0], lin // g.size[0]), p)
-    return p[0], p[1]
-
-
 def test_snapshot_and_stale(R):
     """two rooms, a wall along j = 64 with two doors; a HIMM batch closes the door the paths use"""
     rows = cols = 128
@@ -307,7 +271,7 @@ def test_snapshot_and_stale(R):
     m[64, 20:23] = 0.0
     m[64, 100:103] = 0.0
     master = m.reshape(-1)
-    e, g = make(R, rows, cols, master)
+    e, g = make_engine_and_geom(R, rows, cols, master)
     e.upload(R.capi.LAYER_LASER, master)
     e.compose_master(1)
     goal = 21 + 20 * rows
@@ -351,36 +315,11 @@ def test_snapshot_and_stale(R):
     e.close()
 
 
-class _Hip:
-    def __init__(self):
-        self.h = C.CDLL("libamdhip64.so")
-        self.h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.h.hipFree.argtypes = [C.c_void_p]
-        self.h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-
-    def alloc(self, nbytes):
-        p = C.c_void_p()
-        assert self.h.hipMalloc(C.byref(p), nbytes) == 0
-        return p.value
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        p = self.alloc(a.nbytes)
-        assert self.h.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0
-        return p
-
-    def download(self, p, dtype, count):
-        out = np.empty(count, dtype)
-        assert self.h.hipMemcpy(out.ctypes.data, p, out.nbytes, 2) == 0
-        return out
-
-
 def test_coexists_with_pipelined_batches(R):
-    hip = _Hip()
+    hip = Hip()
     rows = cols = 512
     master = R.synth.obstacles_rect(rows, cols, density=0.3, seed=2)
-    e, g = make(R, rows, cols, master)
+    e, g = make_engine_and_geom(R, rows, cols, master)
     blocked, nbr = O.astar_masks(master, rows, cols)
     e.astar_pipeline_depth(4)
     e.astar_configure(max_queries=64)
@@ -413,10 +352,10 @@ def test_coexists_with_pipelined_batches(R):
 
 def test_bench_size_once(R):
     """the bench's map (4096 x 4096, config 3): the whole field and 256 paths; the device-pointer form gives the same bytes"""
-    hip = _Hip()
+    hip = Hip()
     n = 4096
     master = R.synth.obstacles_rect(n, n)
-    e, g = make(R, n, n, master)
+    e, g = make_engine_and_geom(R, n, n, master)
     blocked, nbr = O.astar_masks(master, n, n)
     q = R.synth.astar_queries(256, master, n, n)
     goal = int(q["goal"][0])
@@ -453,7 +392,7 @@ def test_bench_size_once(R):
 def test_error_paths_on_a_live_engine(R):
     rows, cols = 96, 80
     master = R.synth.obstacles_rect(rows, cols, density=0.1, seed=1)
-    e, g = make(R, rows, cols, master)
+    e, g = make_engine_and_geom(R, rows, cols, master)
     L, h = e._L, e.h
     assert e.goal_field_info()["goal"] == -1 and e.goal_field_ptr() is None
     buf = np.zeros(rows * cols, np.int32)
@@ -491,7 +430,7 @@ def test_goal_on_a_tile_corner_with_its_in_tile_neighbours_blocked(R):
     m[0, 0] = 180.0
     m[64, 65] = m[65, 64] = m[65, 65] = 180.0            # (i, j) = (65, 64), (64, 65), (65, 65)
     master = m.reshape(-1)
-    e, g = make(R, rows, cols, master)
+    e, g = make_engine_and_geom(R, rows, cols, master)
     blocked, nbr = O.astar_masks(master, rows, cols)
     goal = 64 + 64 * rows
     info = e.goal_field(goal)

@@ -10,27 +10,11 @@ import numpy as np
 import pytest
 
 import _oracle as O
+from _gpu import Hip, R, bits, same_f32  # noqa: F401  (R: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "vfh_golden.npz")
-
-
-@pytest.fixture(scope="module")
-def R():
-    import ros_navigation_amd as R
-    R.capi.lib()  # fails loudly when librna.so is missing -- there is no fallback
-    return R
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same_f32(a, b):
-    """bitwise equality, all NaNs treated as equal"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(bits(a)[~np.isnan(a)], bits(b)[~np.isnan(b)])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -583,7 +567,7 @@ def test_bench_configuration_answers_an_unreachable_goal(R):
     q = R.synth.astar_queries(256, master, n, n, seed=2)
     inside = 2006 * n + 1506
     q["goal"][7] = inside
-    hip = _Hip()
+    hip = Hip()
     d_q = hip.upload(q)
     bufs = [(hip.alloc(256 * 2048 * 4), hip.alloc(256 * 24)) for _ in range(2)]
     for d_paths, d_res in bufs:
@@ -602,40 +586,11 @@ def test_bench_configuration_answers_an_unreachable_goal(R):
     e.close()
 
 
-class _Hip:
-    """device buffers for the *_device entry points, through the HIP runtime librna.so itself links"""
-
-    def __init__(self):
-        self.h = C.CDLL("libamdhip64.so")
-        self.h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.h.hipFree.argtypes = [C.c_void_p]
-
-    def alloc(self, nbytes):
-        p = C.c_void_p()
-        assert self.h.hipMalloc(C.byref(p), nbytes) == 0
-        return p.value
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        p = self.alloc(a.nbytes)
-        assert self.h.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0
-        return p
-
-    def download(self, p, dtype, count):
-        out = np.empty(count, dtype)
-        assert self.h.hipMemcpy(out.ctypes.data, p, out.nbytes, 2) == 0
-        return out
-
-    def free(self, p):
-        self.h.hipFree(p)
-
-
 def test_astar_pipelined_batches_with_map_updates_in_between(R):
     """The bench's usage pattern: rna_update_map_device -> rna_astar_batch_device, repeated without waiting, with
     four batches in flight on rotating streams and search fields.  Every batch must see exactly the map of its own
     launch time (the neighbour-mask snapshot) and clean fields (the lazy reset of the stage it reuses)."""
-    hip = _Hip()
+    hip = Hip()
     e = R.Engine(25.6, 25.6, 0.05)   # 512 x 512
     g = O.make_geom(25.6, 25.6, 0.05)
     ref = R.synth.obstacles_rect(e.rows, e.cols, density=0.25, seed=4)
@@ -689,7 +644,7 @@ def test_bench_loop_at_full_size_matches_oracle_every_step(R):
     256 of a batch at once: test_astar_config3_every_bench_query_matches_oracle and bench.py --check-paths), against the
     oracle fed with the same sequence."""
     import bench
-    hip = _Hip()
+    hip = Hip()
     n, nq, rot, depth, max_len = 4096, 256, 4, bench.DEFAULT_PIPELINE, 32768
     steps = -(-3 * depth // rot) * rot   # every stage three times (at least), a whole number of turns of the rotating input sets: 60 for 20 stages
     part = steps // rot          # visits of one query set; each checks every part-th query
@@ -790,7 +745,7 @@ def test_astar_batches_larger_than_max_queries_are_chunked(R):
 
 def test_engines_release_their_hbm(R):
     """create -> plan (pipelined stages, per-stage fields, scheduler state) -> destroy, repeatedly: free HBM returns"""
-    hip = _Hip()
+    hip = Hip()
     hip.h.hipMemGetInfo.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
 
     def free_bytes():

@@ -13,25 +13,12 @@ import pytest
 
 import _oracle as O
 import test_oracle_refpin as T
+from _gpu import R, same_f32  # noqa: F401  (R: the fixture)
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(O.ref_gridmap() is None,
                                  reason="oracle/_ref/libref_gridmap.so is not built (make -C oracle ref where the "
                                         "reference sources are present)")]
-
-
-@pytest.fixture(scope="module")
-def R():
-    import ros_navigation_amd as R
-    R.capi.lib()  # fails loudly when librna.so is missing -- there is no fallback
-    return R
-
-
-def same_f32(a, b):
-    """bitwise equality, all NaNs treated as equal"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and a[~na].view(np.uint32).tobytes() == b[~nb].view(np.uint32).tobytes()
 
 
 def engines(R):

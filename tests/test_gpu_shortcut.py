@@ -19,15 +19,14 @@ import numpy as np
 import pytest
 
 import _oracle as O
+from _gpu import TABLE, Hip, R, make_engine, to_buffer, to_map  # noqa: F401  (R: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NONE = 0xFFFF
 RES = 0.05
 ROWS, COLS = 130, 70
 ESTATE, EINVAL, ECAPACITY = -5, -1, -4
-TABLE = np.array([0, 5000, 4000, 3000, 2000, 1200, 600, 300], np.uint16)   # clearance cost, R = 7
 # neighbour number of the king move (di, dj) in the contract's order (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1)
 MOVE = {(-1, -1): 0, (0, -1): 1, (1, -1): 2, (-1, 0): 3, (1, 0): 4, (-1, 1): 5, (0, 1): 6, (1, 1): 7}
 MOVE_LUT = np.full((3, 3), 8, np.int64)          # [dj + 1, di + 1]
@@ -35,28 +34,8 @@ for (_di, _dj), _k in MOVE.items():
     MOVE_LUT[_dj + 1, _di + 1] = _k
 
 
-@pytest.fixture(scope="module")
-def R():
-    import ros_navigation_amd as R
-    R.capi.lib()
-    return R
-
-
 def make(R, master=None, pos=(0.0, 0.0), rows=ROWS, cols=COLS):
-    e = R.Engine(rows * RES, cols * RES, RES, *pos)
-    assert (e.rows, e.cols) == (rows, cols)
-    if master is not None:
-        e.upload(R.capi.LAYER_MASTER, master)
-    return e
-
-
-def to_map(a, rows, cols, s0, s1):
-    """buffer order -> map order, as a [j, i] array"""
-    return np.roll(np.roll(a.reshape(cols, rows), -s1, axis=0), -s0, axis=1)
-
-
-def to_buffer(a, rows, cols, s0, s1):
-    return np.ascontiguousarray(np.roll(np.roll(a.reshape(cols, rows), s1, axis=0), s0, axis=1).reshape(-1))
+    return make_engine(R, rows, cols, master, pos)
 
 
 def line(a, b):
@@ -472,35 +451,8 @@ def test_keep_clearance(R):
 
 
 # ---- 11. device pointers: chained behind the goal field's paths, and next to a pipelined batch ----
-class _Hip:
-    def __init__(self):
-        self.h = C.CDLL("libamdhip64.so")
-        self.h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.h.hipFree.argtypes = [C.c_void_p]
-        self.h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-
-    def alloc(self, nbytes, zero=True):
-        p = C.c_void_p()
-        assert self.h.hipMalloc(C.byref(p), nbytes) == 0
-        if zero:
-            assert self.h.hipMemset(p, 0, nbytes) == 0
-        return p.value
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        p = self.alloc(a.nbytes, zero=False)
-        assert self.h.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0
-        return p
-
-    def download(self, p, dtype, count):
-        out = np.empty(count, dtype)
-        assert self.h.hipMemcpy(out.ctypes.data, p, out.nbytes, 2) == 0
-        return out
-
-
 def test_device_form_chains_behind_the_goal_field_paths(R):
-    hip = _Hip()
+    hip = Hip()
     m = R.synth.obstacles_rect(ROWS, COLS, density=0.3, seed=7, side=(2, 14))
     e = make(R, m)
     free = np.flatnonzero(R.synth.free_component(m, ROWS, COLS))
@@ -509,8 +461,8 @@ def test_device_form_chains_behind_the_goal_field_paths(R):
     n, max_len, mw = 64, 256, 40
     starts = rng.choice(free, n).astype(np.int32)
     starts[5] = -3
-    d_s, d_paths, d_res = hip.upload(starts), hip.alloc(n * max_len * 4), hip.alloc(n * 24)
-    d_wp, d_out = hip.alloc(n * mw * 4), hip.alloc(n * 16)
+    d_s, d_paths, d_res = hip.upload(starts), hip.alloc(n * max_len * 4, zero=True), hip.alloc(n * 24, zero=True)
+    d_wp, d_out = hip.alloc(n * mw * 4, zero=True), hip.alloc(n * 16, zero=True)
     e.goal_field_paths_device(d_s, n, d_paths, max_len, d_res)
     e.shortcut_paths_device(d_paths, d_res, n, max_len, d_wp, mw, d_out, max_span=50)       # no synchronisation in between
     e.synchronize_map()
@@ -525,7 +477,7 @@ def test_device_form_chains_behind_the_goal_field_paths(R):
 
 
 def test_a_call_while_a_pipelined_batch_is_in_flight(R):
-    hip = _Hip()
+    hip = Hip()
     rows = cols = 512
     m = R.synth.obstacles_rect(rows, cols, density=0.3, seed=2)
     e = make(R, m, rows=rows, cols=cols)
@@ -541,7 +493,8 @@ def test_a_call_while_a_pipelined_batch_is_in_flight(R):
     bufs = []
     for b in range(2):
         q = R.synth.astar_queries(nq, m, rows, cols, seed=20 + b)
-        bufs.append((q, hip.upload(q), hip.alloc(nq * max_len * 4), hip.alloc(nq * 24), hip.alloc(nq * 64 * 4), hip.alloc(nq * 16)))
+        bufs.append((q, hip.upload(q), hip.alloc(nq * max_len * 4, zero=True), hip.alloc(nq * 24, zero=True),
+                     hip.alloc(nq * 64 * 4, zero=True), hip.alloc(nq * 16, zero=True)))
     assert hip.h.hipDeviceSynchronize() == 0
     for q, d_q, d_paths, d_res, d_wp1, d_out1 in bufs:
         e.astar_device(d_q, nq, d_paths, max_len, d_res)
@@ -560,7 +513,7 @@ def test_a_call_while_a_pipelined_batch_is_in_flight(R):
             assert (res["status"][k], res["path_len"][k], res["cost"][k]) == (ores.status, ores.path_len, ores.cost), k
             assert np.array_equal(sp[k][:ores.path_len], opath), k
         # the same call once everything has settled gives what the chained one gave, and both are the oracle's
-        d_wp, d_out = hip.alloc(nq * 64 * 4), hip.alloc(nq * 16)
+        d_wp, d_out = hip.alloc(nq * 64 * 4, zero=True), hip.alloc(nq * 16, zero=True)
         e.shortcut_paths_device(d_paths, d_res, nq, max_len, d_wp, 64, d_out, max_span=64)
         e.synchronize_map()
         got = (hip.download(d_wp, np.int32, nq * 64).reshape(nq, 64), hip.download(d_out, R.capi.SHORTCUT_RESULT_DTYPE, nq))

@@ -10,18 +10,10 @@ import numpy as np
 import pytest
 
 import _oracle as O
+from _gpu import same_f32
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def same_f32(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(bits(a)[~np.isnan(a)], bits(b)[~np.isnan(b)])
 
 
 def test_windowed_himm_is_the_whole_map_update_inside_the_window():

@@ -5,31 +5,16 @@ reference's LineIterator(map, Index, Index) (og_line_cells_index, pinned to the 
 tests/test_oracle_refpin.py), argument checks that need no device, the kernel's resource budget on gfx950, and the C++
 additions compile and link."""
 import ctypes as C
-import os
-import re
 import subprocess
 
 import numpy as np
-import pytest
 
 import _oracle as O
+from _build import (HOST, LIB_DIR, c_values, capi, needs_hipcc, resources,  # noqa: F401  (capi: the fixture)
+                    sources_in_build_files)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ros_navigation_amd", "csrc")
-INCLUDE = os.path.join(ROOT, "include")
-HOST = os.path.join(ROOT, "ros_navigation_amd", "host")
-LIB_DIR = os.path.join(ROOT, "ros_navigation_amd")
-HIPCC = "/opt/rocm/bin/hipcc"
 NEW = ["rna_shortcut_paths", "rna_shortcut_paths_device", "rna_line_cells_index"]
 RNA_EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def capi():
-    import _build
-    _build.native()
-    from ros_navigation_amd import capi
-    return capi
 
 
 def test_new_symbols_are_exported_and_bound(capi):
@@ -44,22 +29,11 @@ def test_new_symbols_are_exported_and_bound(capi):
 
 
 def test_struct_layout_abi_version_and_profile_slots(capi, tmp_path):
-    src = tmp_path / "layout.c"
-    src.write_text(r'''
-#include <stddef.h>
-#include <stdio.h>
-#include "rna.h"
-int main(void) {
+    got = c_values(tmp_path, r'''
   printf("%zu %zu %zu %zu %zu %d %d %d %d\n", sizeof(rna_shortcut_result), offsetof(rna_shortcut_result, status),
          offsetof(rna_shortcut_result, n_waypoints), offsetof(rna_shortcut_result, blocked_steps),
          offsetof(rna_shortcut_result, longest_span), RNA_SHORTCUT_KEEP_CLEARANCE, RNA_SHORTCUT_MAX_PATH_LEN, RNA_ABI_VERSION,
-         (int)RNA_K_COUNT);
-  return 0;
-}
-''')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-I" + INCLUDE, str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+         (int)RNA_K_COUNT);''')
     S, D = capi.ShortcutResult, capi.SHORTCUT_RESULT_DTYPE
     names = ("status", "n_waypoints", "blocked_steps", "longest_span")
     assert got[0] == C.sizeof(S) == D.itemsize == 16
@@ -143,25 +117,12 @@ def test_argument_checks_that_need_no_device(capi):
     assert L.rna_line_cells_index((C.c_int32 * 2)(0, -(1 << 30)), e, buf, 8) == RNA_EINVAL
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@needs_hipcc
 def test_kernel_budget():
     """shortcut.hip cross-compiles for gfx950; both instantiations of the kernel (with and without the clearance test) use no
     scratch, declare no static LDS (the staged path is the launch's dynamic LDS, 4 B per cell) and stay at or below 64 VGPRs
     (one wavefront per path: register pressure is not what limits it, spills would be)."""
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "--offload-arch=gfx950", "-c",
-                          os.path.join(CSRC, "shortcut.hip"), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-        for key in ("VGPRs", r"LDS Size \[bytes/block\]", r"ScratchSize \[bytes/lane\]"):
-            m = re.search(r"remark:\s+" + key + r": (\d+)", line)
-            if m and name:
-                res[name][key.split(" ")[0]] = int(m.group(1))
+    res = resources("shortcut.hip")
     kernels = {k: v for k, v in res.items() if "shortcut_kernel" in k}
     assert len(kernels) == 2 and len(res) == 2, list(res)
     for k, v in kernels.items():
@@ -169,8 +130,7 @@ def test_kernel_budget():
 
 
 def test_sources_are_in_both_build_files():
-    assert re.search(r"^SRCS\s*:=.*\bshortcut\.hip\b", open(os.path.join(CSRC, "Makefile")).read(), re.M)
-    assert re.search(r"set\(RNA_SRCS[^)]*\bshortcut\b", open(os.path.join(ROOT, "CMakeLists.txt")).read())
+    sources_in_build_files("shortcut")
 
 
 def test_cpp_additions_compile_and_link(capi, tmp_path):
