@@ -80,34 +80,136 @@ def check_masks(e, g, master, r):
     return want
 
 
-CASES = [  # rows, cols, position, radii
-    (96, 80, (1.25, -2.5), (0.05, 0.1, 0.25, 0.3, 0.33, 63 * 0.05)),
-    (257, 131, (1000.3, -517.9), (0.05, 0.25, 0.3, 0.33)),
-    (257, 131, (1.25, -2.5), (0.1,)),
-    (96, 80, (1000.3, -517.9), (0.3, 63 * 0.05)),
+SPLIT, INSIDE = "split", "inside"
+LO3, HI3 = float(np.nextafter(0.3, 0.0)), float(np.nextafter(0.3, 1.0))
+# rows, cols, res, position, radii, the map.  A radius given as (r, SPLIT) is a whole number R of cells (or one ulp off it) at a
+# resolution whose arithmetic rounds: the reference must put offset (R, 0) inside the disc in some interior cells and outside
+# in others, or the case would not tell a per-cell tie from a fixed stencil.  (r, INSIDE): res and r are exact in binary,
+# every tie is an equality and (R, 0) is inside in every interior cell.  Both are asked of the reference's lists alone.
+# The map: sample_map, or far_wall() of it for the 63-cell radius, under which sample_map leaves no cell of 70 x 45 free.
+CASES = [
+    (96, 80, 0.05, (1.25, -2.5), (0.05, 0.1, 0.25, 0.3, 0.33, 63 * 0.05), None),
+    (257, 131, 0.05, (1000.3, -517.9), (0.05, 0.25, 0.3, 0.33), None),
+    (257, 131, 0.05, (1.25, -2.5), (0.1,), None),
+    (96, 80, 0.05, (1000.3, -517.9), (0.3, 63 * 0.05), None),
+    # off 0.05 m.  0.1: ties (5, 0) / (4, 3), (3, 0), (10, 0) / (8, 6); 0.25 m = 2.5 cells; 6.3 m = 63 cells, the largest R
+    (70, 45, 0.1, (1.25, -2.5), ((0.5, SPLIT), (0.3, SPLIT), (1.0, SPLIT), 0.25), None),
+    (70, 45, 0.1, (1.25, -2.5), ((6.3, SPLIT),), "far wall"),
+    (130, 67, 0.025, (1.25, -2.5), ((0.125, SPLIT), (0.25, SPLIT)), None),
+    # (1.4 m and not 1.0 m: at x = 1000 the reference puts (5, 0) inside in all 2100 interior cells, (7, 0) in 1395 of 1736)
+    (70, 45, 0.2, (1000.3, -517.9), ((0.6, SPLIT), (1.4, SPLIT)), None),
+    (130, 67, 0.03, (1.25, -2.5), ((0.15, SPLIT), (0.3, SPLIT)), None),
+    (70, 45, 0.07, (1000.3, -517.9), ((0.35, SPLIT),), None),
+    (70, 45, 0.25, (1.25, -2.5), ((1.25, INSIDE),), None),
+    (70, 45, 1.0, (0.5, 0.5), ((5.0, INSIDE),), None),
+    # below a cell, k + 1/2 cells (the box corners p +- r lie on cell boundaries), one ulp either side of six cells
+    (70, 45, 0.05, (1.25, -2.5), (1e-9, 0.025, 0.075, 0.125, (LO3, SPLIT), (HI3, SPLIT)), None),
+    # every cell an edge cell: the plan is made for coordinates of 6e12 m, eta = 2^-48 * 6e12 = 0.021 m, 16 eta >= res, so
+    # make_plan sets band = 1 << 30 and every cell asks box_is_plain.  (Cell centres lie on a grid of 2^-11 m there.)
+    (70, 45, 0.05, (3.0e12, -1.0e12), ((0.3, SPLIT), 0.25), None),
 ]
 
 
-@pytest.mark.parametrize("rows,cols,pos,radii", CASES)
-def test_blocked_set_matches_reference_predicate(R, rows, cols, pos, radii):
+def offset_R0_inside(g, r):
+    """From the reference's disc lists alone: for every interior cell (at least R = round(r / res) cells from every edge of
+    the map), whether the cell R rows on, offset (R, 0), is in its disc.  No cell of a 70 x 45 map is 63 cells from every
+    edge: there the cells whose offset (R, 0) is in the map stand in."""
+    rows, cols = g.size[0], g.size[1]
+    R = int(round(r / g.res))
+    offs, idx = disc_lists(g, r)
+    cell = np.repeat(np.arange(rows * cols), np.diff(offs))
+    inside = np.zeros(rows * cols, bool)
+    inside[cell[idx == (cell % rows + R) % rows + cell // rows * rows]] = True
+    lin = np.arange(rows * cols)
+    i, j = (lin % rows - g.start[0]) % rows, (lin // rows - g.start[1]) % cols        # map space
+    interior = (i >= R) & (i < rows - R) & (j >= R) & (j < cols - R)
+    if not interior.any():
+        interior = i < rows - R
+    assert interior.any()
+    return inside[interior]
+
+
+def check_expectation(g, r, expect):
+    inside = offset_R0_inside(g, r)
+    if expect == SPLIT:
+        assert 0 < inside.sum() < inside.size, ("the reference decides offset (R, 0) alike in every cell", r, int(inside.sum()))
+    else:
+        assert inside.all(), ("an exact tie outside the reference's disc", r, int(inside.sum()), inside.size)
+
+
+def far_wall(master, rows, cols):
+    """sample_map with its obstacles kept in rows 0-1 only and a wall along row 2, gaps where the cell is unknown: whether
+    cell (2 + R, j) is blocked is then the reference's decision on offset (-R, 0) in that cell (the next offsets, (-R, +-1),
+    are a cell outside), and the cells beyond are free"""
+    m = master.reshape(cols, rows).copy()
+    m[:, 2:][m[:, 2:] > 0] = 0.0
+    m[:, 2][~np.isnan(m[:, 2])] = 100.0
+    return m.reshape(-1)
+
+
+def case_id(k, c):
+    """(the four cases at 0.05 m keep the names they had before the resolution became a parameter)"""
+    return "%d-%d-pos%d-radii%d" % (c[0], c[1], k, k) if k < 4 else "%d-%d-res%g-pos%d%s" % (c[0], c[1], c[2], k, "-far-wall" if c[5] else "")
+
+
+@pytest.mark.parametrize("rows,cols,res,pos,radii,wall", CASES, ids=[case_id(k, c) for k, c in enumerate(CASES)])
+def test_blocked_set_matches_reference_predicate(R, rows, cols, res, pos, radii, wall):
     master = sample_map(rows, cols, seed=rows + cols)
-    e, g = make_engine_and_geom(R, rows, cols, master, pos)
+    if wall:
+        master = far_wall(master, rows, cols)
+    e, g = make_engine_and_geom(R, rows, cols, master, pos, res=res)
     for r in radii:
+        r, expect = r if isinstance(r, tuple) else (r, None)
+        if expect:
+            check_expectation(g, r, expect)
         assert e.astar_robot_radius(r) == r
-        check_masks(e, g, master, r)
+        blocked = check_masks(e, g, master, r)
+        if (res, r) != (0.05, 63 * 0.05):           # (the two first cases of 63 cells: every cell blocked, kept as they were)
+            assert 0 < blocked.sum() < blocked.size, r
     e.close()
 
 
-def test_blocked_set_on_a_moved_map(R):
-    rows, cols = 96, 80
+@pytest.mark.parametrize("rows,cols,res,target,radii", [(96, 80, 0.05, (2.33, -1.61), (0.3, 0.25, 63 * 0.05)),
+                                                        (70, 45, 0.1, (2.33, -1.64), ((0.5, SPLIT), (0.3, SPLIT)))])
+def test_blocked_set_on_a_moved_map(R, rows, cols, res, target, radii):
+    """(the second target is 10.8 and 8.6 cells of 0.1 m from (1.25, -2.5): no multiple of the resolution on either axis)"""
     master = sample_map(rows, cols, seed=5)
-    e, g = make_engine_and_geom(R, rows, cols, master, (1.25, -2.5))
-    e.astar_robot_radius(0.3)
-    check_masks(e, g, master, 0.3)
-    ref = move_both(R, e, g, master, (2.33, -1.61))
-    for r in (0.3, 0.25, 63 * 0.05):
+    e, g = make_engine_and_geom(R, rows, cols, master, (1.25, -2.5), res=res)
+    first = radii[0][0] if isinstance(radii[0], tuple) else radii[0]
+    e.astar_robot_radius(first)
+    check_masks(e, g, master, first)
+    ref = move_both(R, e, g, master, target)
+    for r in radii:
+        r, expect = r if isinstance(r, tuple) else (r, None)
+        if expect:
+            check_expectation(g, r, expect)
         e.astar_robot_radius(r)
-        check_masks(e, g, ref, r)
+        blocked = check_masks(e, g, ref, r)
+        assert r == 63 * 0.05 or 0 < blocked.sum() < blocked.size, r
+    e.close()
+
+
+def test_far_move_remakes_the_stencil_plan_and_the_way_back_keeps_it(R):
+    """footprint_refresh makes its plan for twice the geometry's coordinate magnitude and re-makes it when a move exceeds
+    that (mag > e->fp.mag).  (1.25, -2.5) -> (40000.7, -25000.3) -> (1.4, -2.6), which is three and two cells from where it
+    began so that the buffer stays a moved one.  The second comparison runs under a plan re-made for the far origin, the
+    third under that same plan, made for some ten thousand times the magnitude the geometry then has (wider margins).  A
+    move that far leaves only NaN, so a fresh map is written on both sides, in buffer order."""
+    rows, cols, r = 70, 45, 0.3
+    near, far, back = (1.25, -2.5), (40000.7, -25000.3), (1.4, -2.6)
+    master = sample_map(rows, cols, seed=31)
+    e, g = make_engine_and_geom(R, rows, cols, master, near)
+    assert e.astar_robot_radius(r) == r
+    check_masks(e, g, master, r)
+    for k, target in enumerate((far, back)):
+        left = move_both(R, e, g, master, target)
+        assert np.isnan(left).all() and np.isnan(e.download(R.capi.LAYER_MASTER)).all()
+        assert tuple(g.pos) == tuple(e.geometry().position) and abs(g.pos[0] - target[0]) < 0.05
+        master = sample_map(rows, cols, seed=32 + k)          # buffer order, the same bytes on both sides
+        e.upload(R.capi.LAYER_MASTER, master)
+        blocked = check_masks(e, g, master, r)
+        assert 0 < blocked.sum() < blocked.size
+        check_expectation(g, r, SPLIT)
     e.close()
 
 
@@ -142,11 +244,15 @@ def queries(rng, blocked, n, want_band):
     return q
 
 
-@pytest.mark.parametrize("rows,cols,pos,r,moved", [(96, 80, (1.25, -2.5), 0.3, False), (257, 131, (1000.3, -517.9), 0.25, False),
-                                                   (257, 131, (1.25, -2.5), 0.3, True)])
-def test_search_matches_oracle(R, rows, cols, pos, r, moved):
+SEARCHES = [(96, 80, 0.05, (1.25, -2.5), 0.3, False), (257, 131, 0.05, (1000.3, -517.9), 0.25, False),
+            (257, 131, 0.05, (1.25, -2.5), 0.3, True), (130, 67, 0.1, (1.25, -2.5), 0.5, True)]
+
+
+@pytest.mark.parametrize("rows,cols,res,pos,r,moved", SEARCHES,   # (the ids of the cases at 0.05 m: as they were without `res`)
+                         ids=["%d-%d-%spos%d-%s-%s" % (c[0], c[1], "" if k < 3 else "res%g-" % c[2], k, c[4], c[5]) for k, c in enumerate(SEARCHES)])
+def test_search_matches_oracle(R, rows, cols, res, pos, r, moved):
     master = sample_map(rows, cols, seed=7 + rows, occupied=0.002)
-    e, g = make_engine_and_geom(R, rows, cols, master, pos)
+    e, g = make_engine_and_geom(R, rows, cols, master, pos, res=res)
     if moved:
         master = move_both(R, e, g, master, (pos[0] + 3.37, pos[1] - 1.12))
     e.astar_robot_radius(r)
@@ -234,25 +340,54 @@ def test_incremental_refresh_equals_full_rebuild(R):
     e.close()
 
 
-def test_if_blocked_matches_reference_predicate(R):
-    rows, cols, pos, res = 96, 80, (1.25, -2.5), 0.05
+# rna_if_blocked_batch[_device]: rows, cols, res, moved to, radii (a whole number of cells, k + 1/2 cells, and one larger
+# than the margin by which the positions go outside: 0.6 m, which is 6 cells at 0.1 m)
+IF_BLOCKED = [(96, 80, 0.05, None, (0.1, 0.3, 0.125, 1.0)), (70, 45, 0.1, None, (0.5, 0.25, 1.0)),
+              (96, 80, 0.05, (2.33, -1.61), (0.3, 0.125, 1.0))]
+_if_blocked_want = {}
+
+
+def if_blocked_setup(R, case):
+    """the engine, the oracle's geometry, the master and the 10 000 positions of a case of IF_BLOCKED: uniform up to the
+    margin outside the map, 1000 on its x edges, 1000 on its y edges, 1000 on cell corners, from that geometry's bounds"""
+    rows, cols, res, target, radii = IF_BLOCKED[case]
     master = sample_map(rows, cols, seed=21)
-    e, g = make_engine_and_geom(R, rows, cols, master, pos)
-    occ = (~np.isnan(master)) & (master > 0)
+    e, g = make_engine_and_geom(R, rows, cols, master, (1.25, -2.5), res=res)
+    if target:
+        master = move_both(R, e, g, master, target)
     rng = np.random.default_rng(4)
     L = np.array([rows * res, cols * res])
-    lo, hi = np.array(pos) - L / 2, np.array(pos) + L / 2
-    xy = rng.uniform(lo - 0.6, hi + 0.6, (10000, 2))
+    lo, hi = np.array(g.pos) - L / 2, np.array(g.pos) + L / 2
+    margin = max(0.6, 6 * res)
+    xy = rng.uniform(lo - margin, hi + margin, (10000, 2))
     xy[:1000, 0] = rng.choice([lo[0], hi[0]], 1000)                      # on the map's edges
     xy[1000:2000, 1] = rng.choice([lo[1], hi[1]], 1000)
-    xy[2000:3000] = lo + res * rng.integers(0, 97, (1000, 2))           # on cell corners
-    for r in (0.1, 0.3, 1.0):
-        got = e.if_blocked(xy, r)
+    xy[2000:3000] = lo + res * rng.integers(0, rows + 1, (1000, 2))     # on cell corners
+    assert max(radii) > margin
+    return e, g, master, xy, radii
+
+
+def if_blocked_want(case, g, master, xy, r):
+    """the reference's answer at every position, computed once for the host and the device-pointer test"""
+    if (case, r) not in _if_blocked_want:
+        rows, cols = g.size[0], g.size[1]
+        occ = (~np.isnan(master)) & (master > 0)
         want = np.zeros(len(xy), np.uint8)
         for k in range(len(xy)):
             c = O.circle_cells(g, tuple(xy[k]), r, reference=REFERENCE)
             ok = (c[:, 0] >= 0) & (c[:, 0] < rows) & (c[:, 1] >= 0) & (c[:, 1] < cols)
             want[k] = occ[c[ok, 0] + c[ok, 1] * rows].any()
+        want.flags.writeable = False
+        _if_blocked_want[(case, r)] = want
+    return _if_blocked_want[(case, r)]
+
+
+@pytest.mark.parametrize("case", range(len(IF_BLOCKED)))
+def test_if_blocked_matches_reference_predicate(R, case):
+    e, g, master, xy, radii = if_blocked_setup(R, case)
+    for r in radii:
+        got = e.if_blocked(xy, r)
+        want = if_blocked_want(case, g, master, xy, r)
         bad = np.flatnonzero(got != want)
         assert bad.size == 0, (r, xy[bad[:5]], got[bad[:5]])
         if r == 0.3:
@@ -261,6 +396,27 @@ def test_if_blocked_matches_reference_predicate(R):
         assert 0 < got.sum() < len(xy)
     with pytest.raises(R.capi.RnaError):
         e.if_blocked(xy[:4], -0.1)
+    e.close()
+
+
+@pytest.mark.parametrize("case", range(len(IF_BLOCKED)))
+def test_if_blocked_device_pointers_answer_as_the_host_entry(R, case):
+    """rna_if_blocked_batch_device on positions and an output buffer of the caller's: the same bytes as the host entry and
+    as the reference.  (The output buffer starts as 0xEE: every byte must have been written.)"""
+    hip = Hip()
+    e, g, master, xy, radii = if_blocked_setup(R, case)
+    d_xy, d_out = hip.upload(xy), hip.alloc(len(xy))
+    for r in radii:
+        assert hip.h.hipMemset(d_out, 0xEE, len(xy)) == 0
+        e.if_blocked_device(d_xy, len(xy), r, d_out)
+        e.synchronize()
+        got = hip.download(d_out, np.uint8, len(xy))
+        assert got.tobytes() == e.if_blocked(xy, r).tobytes()
+        assert got.tobytes() == if_blocked_want(case, g, master, xy, r).tobytes(), r
+    with pytest.raises(R.capi.RnaError):
+        e.if_blocked_device(d_xy, 4, -0.1, d_out)
+    hip.free(d_xy)
+    hip.free(d_out)
     e.close()
 
 

@@ -2,7 +2,8 @@
 hours) with a FIXED seed and a short budget each, as subprocesses -- random map shapes that are not multiples of the
 64 x 16 search tiles, densities 0..0.6, unknown cells, bucket widths 2828..400000, chunked batches, engine reuse, maps
 moved once or twice (grid A*); random geometry / resolution / moved buffers, end points on cell centres, edges and the
-map border, poses past the border (map update + VFH+).  A fuzzer exits non-zero at the first difference from the oracle
+map border, poses past the border (map update + VFH+); resolutions 0.025-0.2 m, origins up to 2000 m, radii of k and k + 1/2
+cells, moved maps (robot radius).  A fuzzer exits non-zero at the first difference from the oracle
 and prints the configuration that reproduces it.  The search kernel's correctness rests on an asynchronous scheduler,
 `asm volatile` fences and on what the optimiser may hoist: this net catches what the hand-picked cases do not."""
 import os
@@ -32,3 +33,12 @@ def test_fuzz_grid_astar_fixed_seed(seed):
 
 def test_fuzz_map_update_and_vfh_fixed_seed():
     run_fuzzer("fuzz_himm_vfh.py", 15, 303)
+
+
+def test_fuzz_footprint_fixed_seed():
+    text = run_fuzzer("fuzz_footprint.py", 10, 304)
+    maps = int(text.split("):")[1].split("maps")[0])
+    # The per-cell oracle in Python is what a case costs.  Measured on a CPU-only machine, with the engine's answers replaced
+    # by the oracle's own so that only the oracle side runs: 25 maps in 10 s with this seed (16 and 24 with seeds 1 and 2).
+    # The floor is below half of that, because the GPU host's CPUs are shared.
+    assert maps >= 8, text
