@@ -9,7 +9,7 @@
 // minimum over the rows |dj| <= R of those is the minimum over all cells with |dj| <= R, |di| <= 63 -- a superset of the disc
 // of radius R <= 63.  Cells outside the map hold no bit (CircleIterator does not visit them either).
 #include "engine.hpp"
-#include "compose_dev.hpp"
+#include "map_tiles_dev.hpp"
 
 #include <algorithm>
 
@@ -19,10 +19,6 @@ namespace {
 
 constexpr int CLR_MAX_R = 63;                        // the footprint's bound: a tile needs its one-tile ring only
 constexpr int CLR_ROWS = TILE + 2 * CLR_MAX_R;       // blocked-bit rows of a workgroup (halo R on each side)
-
-__device__ __forceinline__ unsigned long long clr_funnel(unsigned long long lo, unsigned long long hi, int s) {
-  return s ? (lo >> s) | (hi << (64 - s)) : lo;
-}
 
 }  // namespace
 
@@ -39,43 +35,16 @@ __global__ void __launch_bounds__(256) clearance_tiles_kernel(uint16_t* __restri
   __shared__ unsigned long long occ[CLR_ROWS][4];
   const int ti = blockIdx.x, tj = blockIdx.y, tiles_i = gridDim.x;
   const int i0 = ti * TILE, j0 = tj * TILE;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nrow = TILE + 2 * R;   // <= CLR_ROWS (1 <= R <= CLR_MAX_R, checked by the host)
   if (bits) {
     // a thread per (row, word): the word of row j in tile (ti - 1 + word, j / 64), or 0 outside the map
     for (int k = threadIdx.x; k < nrow * 4; k += blockDim.x) {
       const int jj = k >> 2, word = k & 3;
       const int j = j0 - R + jj, a = ti - 1 + word;
-      unsigned long long m = 0ull;
-      if (word < 3 && a >= 0 && a < tiles_i && j >= 0 && j < cols) m = bits[((size_t)(j / TILE) * tiles_i + a) * TILE + (j % TILE)];
-      occ[jj][word] = m;
+      occ[jj][word] = word < 3 ? fp_bits_word(bits, tiles_i, cols, a, j) : 0ull;
     }
   } else {
-    // a wavefront per pair of rows: the six reads (3 words x 2 rows, 64 cells each) leave together, then one ballot per word
-    for (int jj0 = 2 * wave; jj0 < nrow; jj0 += 8) {
-      float v[2][3];
-      bool ok[2][3];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int word = 0; word < 3; ++word) {
-          const int i = i0 - 64 + word * 64 + lane, j = j0 - R + jj0 + u;
-          ok[u][word] = jj0 + u < nrow && i >= i0 - R && i < i0 + TILE + R && i >= 0 && j >= 0 && i < rows && j < cols;
-          const int bi = i + s0 >= rows ? i + s0 - rows : i + s0;
-          const int bj = j + s1 >= cols ? j + s1 - cols : j + s1;
-          v[u][word] = master[ok[u][word] ? (size_t)bj * rows + bi : 0];   // (cell 0 for lanes without a cell: read, not used)
-        }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        if (jj0 + u >= nrow) break;   // (uniform)
-#pragma unroll
-        for (int word = 0; word < 3; ++word) {
-          const unsigned long long m = __ballot(ok[u][word] && cell_blocked(v[u][word]));
-          if (lane == 0) occ[jj0 + u][word] = m;
-        }
-        if (lane == 0) occ[jj0 + u][3] = 0ull;
-      }
-    }
+    occ_rows_load(occ, master, i0, j0, R, rows, cols, s0, s1);
   }
   __syncthreads();
   const int none = R * R + 1;
@@ -84,24 +53,20 @@ __global__ void __launch_bounds__(256) clearance_tiles_kernel(uint16_t* __restri
     const int i = i0 + li, j = j0 + lj;
     if (i >= rows || j >= cols) continue;
     const int p = li + 64;                      // the cell's bit in its row (64 .. 127)
-    const int q1 = p - 63, k1 = q1 >> 6, sh1 = q1 & 63, k2 = p >> 6, sh2 = p & 63;
     const int jc = lj + R;                      // the cell's row in occ
     int best = none;
     for (int dj = 0; dj * dj < best; ++dj) {    // (dj <= R: (R + 1)^2 >= none)
 #pragma unroll
       for (int side = 0; side < 2; ++side) {
         if (side && !dj) continue;
-        const unsigned long long* o = occ[side ? jc - dj : jc + dj];
-        const unsigned long long lo = clr_funnel(o[k1], o[k1 + 1], sh1);   // bits p - 63 .. p: the cell is bit 63
-        const unsigned long long hi = clr_funnel(o[k2], o[k2 + 1], sh2);   // bits p .. p + 63: the cell is bit 0
+        unsigned long long lo, hi;   // the cell is bit 63 of lo, bit 0 of hi
+        occ_windows(occ[side ? jc - dj : jc + dj], p, lo, hi);
         const int dl = lo ? __clzll((long long)lo) : 64, dr = hi ? __ffsll((long long)hi) - 1 : 64;
         const int d = min(dl, dr);
         if (d < 64) best = min(best, dj * dj + d * d);
       }
     }
-    const int bi = i + s0 >= rows ? i + s0 - rows : i + s0;
-    const int bj = j + s1 >= cols ? j + s1 - cols : j + s1;
-    clr[(size_t)bj * rows + bi] = best < none ? (uint16_t)best : (uint16_t)RNA_CLEARANCE_NONE;
+    clr[buffer_lin(i, j, rows, cols, s0, s1)] = best < none ? (uint16_t)best : (uint16_t)RNA_CLEARANCE_NONE;
   }
 }
 

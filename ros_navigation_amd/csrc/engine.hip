@@ -4,7 +4,7 @@
 //   MapProvider::composeMasterMapFromLayerdMap  mc/src/map_provider.cpp:216-223
 //   GridMap::move                          gmc/src/GridMap.cpp:346-412
 #include "engine.hpp"
-#include "compose_dev.hpp"
+#include "map_tiles_dev.hpp"
 
 #include <cmath>
 #include <dirent.h>
@@ -42,8 +42,6 @@ __global__ void compose_dirty_tiles_kernel(float* __restrict__ master, const flo
   }
 }
 
-// (cell_blocked -- GlobalPlanner::ifBlocked's predicate -- lives in compose_dev.hpp)
-
 // Per-cell 8-bit traversable-neighbour mask (DESIGN.md "Grid A* contract"): bit k <-> neighbour
 // (di,dj) in the order (-1,-1),(0,-1),(1,-1),(-1,0),(1,0),(-1,1),(0,1),(1,1); a diagonal needs the
 // target and both orthogonal cells free.  One block per 64x64 tile with a 1-cell halo in LDS.
@@ -56,17 +54,7 @@ __global__ void nbr_mask_tiles_kernel(uint8_t* __restrict__ nbr, const float* __
                                       const unsigned* __restrict__ dirty, int all, int rows, int cols,
                                       int tiles_i, int tiles_j, int s0, int s1) {
   const int ti = blockIdx.x, tj = blockIdx.y;
-  if (!all) {
-    bool need = false;
-    for (int dj = -1; dj <= 1 && !need; ++dj)
-      for (int di = -1; di <= 1; ++di) {
-        const int a = ti + di, b = tj + dj;
-        if (a < 0 || b < 0 || a >= tiles_i || b >= tiles_j) continue;
-        const int t = b * tiles_i + a;
-        if (reinterpret_cast<const unsigned char*>(dirty)[t]) { need = true; break; }
-      }
-    if (!need) return;
-  }
+  if (!all && !dirty_ring(dirty, ti, tj, tiles_i, tiles_j)) return;
   __shared__ uint8_t blk[(TILE + 2) * (TILE + 2)];  // [jj][ii], ii fastest; out of map = blocked
   const int i0 = ti * TILE - 1, j0 = tj * TILE - 1;
   for (int k = threadIdx.x; k < (TILE + 2) * (TILE + 2); k += blockDim.x) {
@@ -74,10 +62,7 @@ __global__ void nbr_mask_tiles_kernel(uint8_t* __restrict__ nbr, const float* __
     const int i = i0 + ii, j = j0 + jj;
     uint8_t b = 1;
     if (i >= 0 && j >= 0 && i < rows && j < cols) {
-      int bi = i + s0, bj = j + s1;
-      if (bi >= rows) bi -= rows;
-      if (bj >= cols) bj -= cols;
-      b = cell_blocked(master[(size_t)bj * rows + bi]) ? 1 : 0;
+      b = cell_blocked(master[buffer_lin(i, j, rows, cols, s0, s1)]) ? 1 : 0;
     }
     blk[k] = b;
   }
@@ -86,24 +71,7 @@ __global__ void nbr_mask_tiles_kernel(uint8_t* __restrict__ nbr, const float* __
     const int li = k & (TILE - 1), lj = k >> 6;
     const int i = ti * TILE + li, j = tj * TILE + lj;
     if (i >= rows || j >= cols) continue;
-    const uint8_t* c = &blk[(lj + 1) * (TILE + 2) + (li + 1)];
-    constexpr int S = TILE + 2;
-    unsigned m = 0;
-    if (!c[0]) {
-      const bool up = !c[-1], dn = !c[1], lf = !c[-S], rt = !c[S];
-      if (lf && up && !c[-S - 1]) m |= 1u;        // (-1,-1)
-      if (lf) m |= 2u;                            // ( 0,-1)
-      if (lf && dn && !c[-S + 1]) m |= 4u;        // ( 1,-1)
-      if (up) m |= 8u;                            // (-1, 0)
-      if (dn) m |= 16u;                           // ( 1, 0)
-      if (rt && up && !c[S - 1]) m |= 32u;        // (-1, 1)
-      if (rt) m |= 64u;                           // ( 0, 1)
-      if (rt && dn && !c[S + 1]) m |= 128u;       // ( 1, 1)
-    }
-    int bi = i + s0, bj = j + s1;
-    if (bi >= rows) bi -= rows;
-    if (bj >= cols) bj -= cols;
-    nbr[(size_t)bj * rows + bi] = (uint8_t)m;
+    nbr[buffer_lin(i, j, rows, cols, s0, s1)] = (uint8_t)nbr_mask_of(&blk[(lj + 1) * (TILE + 2) + (li + 1)], TILE + 2);
   }
 }
 
@@ -194,10 +162,7 @@ __global__ void submap_gather_kernel(const float* __restrict__ layer, int rows, 
   const size_t n = (size_t)sr * sc;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
-    int bi = tl0 + (int)(k % sr), bj = tl1 + (int)(k / sr);
-    if (bi >= rows) bi -= rows;
-    if (bj >= cols) bj -= cols;
-    out[k] = layer[(size_t)bj * rows + bi];
+    out[k] = layer[buffer_lin((int)(k % sr), (int)(k / sr), rows, cols, tl0, tl1)];
   }
 }
 

@@ -5,14 +5,14 @@
 //
 // With a radius r > 0 a cell c is blocked for the search iff some cell CircleIterator(map, getPosition(c), r) visits holds
 // a finite master value > 0.  footprint_tiles_kernel computes that set for 64 x 64 tiles by dilating the tile's occupancy
-// bits with the disc stencil of FootprintPlan, and the neighbour masks from it by the rule of nbr_mask_tiles_kernel.
+// bits with the disc stencil of FootprintPlan, and the neighbour masks from it by the rule of nbr_mask_tiles_kernel (nbr_mask_of).
 // Why the dilation is exact (DESIGN.md "Robot radius"): the stencil's sure-in / sure-out offsets are decided with a margin
 // that bounds the rounding of the reference's f64 cell-centre arithmetic; the few offsets inside the margin (ties, e.g.
 // (6, 0) for 0.3 m at 0.05 m) are evaluated per cell with the reference's own expressions; and every cell near the map
 // edge computes its bounding box as the reference does and, where that box is not the plain one, runs the whole
 // procedure (disc_blocked) instead.
 #include "engine.hpp"
-#include "compose_dev.hpp"
+#include "map_tiles_dev.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -80,10 +80,6 @@ __device__ bool box_is_plain(const Geom& g, double px, double py, double radius,
          tu[1] < g.size[1];
 }
 
-__device__ __forceinline__ unsigned long long funnel64(unsigned long long lo, unsigned long long hi, int s) {
-  return s ? (lo >> s) | (hi << (64 - s)) : lo;
-}
-
 }  // namespace
 
 // One workgroup per 64 x 64 tile (MAP space, unwrapped indices; (s0, s1) = buffer start index, as nbr_mask_tiles_kernel):
@@ -92,7 +88,7 @@ __device__ __forceinline__ unsigned long long funnel64(unsigned long long lo, un
 //  2. the blocked byte of every cell of the tile and its 1-cell ring (outside the map: blocked, for the moves): the OR over
 //     the stencil rows dj of "a bit within [i - w(dj), i + w(dj)] of row j + dj" (two 64-bit windows around the cell),
 //     then the tie offsets in f64, then -- near the map edge -- the bounding-box check and, where it fails, disc_blocked;
-//  3. the tile's blocked bits and its cells' 8-bit neighbour masks (the rule of nbr_mask_tiles_kernel).
+//  3. the tile's blocked bits and its cells' 8-bit neighbour masks (nbr_mask_of).
 // `all` != 0: every tile; otherwise only tiles that are dirty or touch a dirty tile (unmoved map).
 __global__ void __launch_bounds__(256) footprint_tiles_kernel(uint8_t* __restrict__ nbr, unsigned long long* __restrict__ bits,
                                                               const float* __restrict__ master, const unsigned* __restrict__ dirty,
@@ -100,48 +96,13 @@ __global__ void __launch_bounds__(256) footprint_tiles_kernel(uint8_t* __restric
   const int ti = blockIdx.x, tj = blockIdx.y;
   const int tiles_i = gridDim.x, tiles_j = gridDim.y;
   const int rows = g.size[0], cols = g.size[1];
-  if (!all) {
-    bool need = false;
-    for (int dj = -1; dj <= 1 && !need; ++dj)
-      for (int di = -1; di <= 1; ++di) {
-        const int a = ti + di, b = tj + dj;
-        if (a < 0 || b < 0 || a >= tiles_i || b >= tiles_j) continue;
-        if (reinterpret_cast<const unsigned char*>(dirty)[b * tiles_i + a]) { need = true; break; }
-      }
-    if (!need) return;
-  }
+  if (!all && !dirty_ring(dirty, ti, tj, tiles_i, tiles_j)) return;
   __shared__ unsigned long long occ[FP_ROWS][4];
   __shared__ uint8_t blk[FP_BLK * FP_BLK];
   const int R = P.R, H = R + 1;
   const int i0 = ti * TILE, j0 = tj * TILE;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int nrow = TILE + 2 * H;
-  // 1. a wavefront per pair of occupancy rows: the six reads (3 words x 2 rows, 64 cells each) leave together, then one
-  //    ballot per word.  (A read per (row, word) and trip left the loads of a wavefront one memory round trip apart.)
-  for (int jj0 = 2 * wave; jj0 < nrow; jj0 += 8) {
-    float v[2][3];
-    bool ok[2][3];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int word = 0; word < 3; ++word) {
-        const int i = i0 - 64 + word * 64 + lane, j = j0 - H + jj0 + u;
-        ok[u][word] = jj0 + u < nrow && i >= i0 - H && i < i0 + TILE + H && i >= 0 && j >= 0 && i < rows && j < cols;
-        const int bi = i + g.start[0] >= rows ? i + g.start[0] - rows : i + g.start[0];
-        const int bj = j + g.start[1] >= cols ? j + g.start[1] - cols : j + g.start[1];
-        v[u][word] = master[ok[u][word] ? (size_t)bj * rows + bi : 0];   // (cell 0 for lanes without a cell: read, not used)
-      }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (jj0 + u >= nrow) break;   // (uniform)
-#pragma unroll
-      for (int word = 0; word < 3; ++word) {
-        const unsigned long long m = __ballot(ok[u][word] && cell_blocked(v[u][word]));
-        if (lane == 0) occ[jj0 + u][word] = m;
-      }
-      if (lane == 0) occ[jj0 + u][3] = 0ull;
-    }
-  }
+  occ_rows_load(occ, master, i0, j0, H, rows, cols, g.start[0], g.start[1]);   // 1. (map_tiles_dev.hpp)
   __syncthreads();
   // 2. blocked bytes of the tile and its ring
   const double ox = g.pos[0] + (0.5 * g.len[0] - 0.5 * g.res), oy = g.pos[1] + (0.5 * g.len[1] - 0.5 * g.res);
@@ -152,15 +113,13 @@ __global__ void __launch_bounds__(256) footprint_tiles_kernel(uint8_t* __restric
     uint8_t out = 1;
     if (i >= 0 && j >= 0 && i < rows && j < cols) {
       const int p = li + 64;                    // the cell's bit in its occupancy row (63 .. 128)
-      const int q1 = p - 63, k1 = q1 >> 6, s1 = q1 & 63, k2 = p >> 6, s2 = p & 63;
       const int jc = lj + H;                    // the cell's occupancy row
       bool hit = false;
       for (int dj = -R; dj <= R; ++dj) {
         const int w = P.w[dj < 0 ? -dj : dj];
         if (w < 0) continue;
-        const unsigned long long* o = occ[jc + dj];
-        const unsigned long long lo = funnel64(o[k1], o[k1 + 1], s1);   // bits p - 63 .. p
-        const unsigned long long hi = funnel64(o[k2], o[k2 + 1], s2);   // bits p .. p + 63
+        unsigned long long lo, hi;
+        occ_windows(occ[jc + dj], p, lo, hi);
         if ((lo >> (63 - w)) | (hi << (63 - w))) hit = true;
       }
       const double px = ox + g.res * (double)(-i), py = oy + g.res * (double)(-j);
@@ -184,29 +143,13 @@ __global__ void __launch_bounds__(256) footprint_tiles_kernel(uint8_t* __restric
     const int i = i0 + lane, j = j0 + lj;
     const bool b = i < rows && j < cols && blk[(lj + 1) * FP_BLK + lane + 1];
     const unsigned long long m = __ballot(b);
-    if (lane == 0) bits[((size_t)tj * tiles_i + ti) * TILE + lj] = m;
+    if (lane == 0) bits[fp_bits_index(tiles_i, ti, j)] = m;
   }
   for (int k = threadIdx.x; k < TILE * TILE; k += blockDim.x) {
     const int li = k & (TILE - 1), lj = k >> 6;
     const int i = i0 + li, j = j0 + lj;
     if (i >= rows || j >= cols) continue;
-    const uint8_t* c = &blk[(lj + 1) * FP_BLK + (li + 1)];
-    constexpr int S = FP_BLK;
-    unsigned m = 0;
-    if (!c[0]) {
-      const bool up = !c[-1], dn = !c[1], lf = !c[-S], rt = !c[S];
-      if (lf && up && !c[-S - 1]) m |= 1u;        // (-1,-1)
-      if (lf) m |= 2u;                            // ( 0,-1)
-      if (lf && dn && !c[-S + 1]) m |= 4u;        // ( 1,-1)
-      if (up) m |= 8u;                            // (-1, 0)
-      if (dn) m |= 16u;                           // ( 1, 0)
-      if (rt && up && !c[S - 1]) m |= 32u;        // (-1, 1)
-      if (rt) m |= 64u;                           // ( 0, 1)
-      if (rt && dn && !c[S + 1]) m |= 128u;       // ( 1, 1)
-    }
-    const int bi = i + g.start[0] >= rows ? i + g.start[0] - rows : i + g.start[0];
-    const int bj = j + g.start[1] >= cols ? j + g.start[1] - cols : j + g.start[1];
-    nbr[(size_t)bj * rows + bi] = (uint8_t)m;
+    nbr[buffer_lin(i, j, rows, cols, g.start[0], g.start[1])] = (uint8_t)nbr_mask_of(&blk[(lj + 1) * FP_BLK + (li + 1)], FP_BLK);
   }
 }
 
@@ -216,10 +159,9 @@ __global__ void blocked_bytes_kernel(uint8_t* __restrict__ out, const unsigned l
   const size_t n = (size_t)rows * cols;
   for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x) {
     if (!bits) { out[k] = cell_blocked(master[k]) ? 1 : 0; continue; }
-    const int bi = (int)(k % rows), bj = (int)(k / rows);
-    const int i = bi - s0 < 0 ? bi - s0 + rows : bi - s0, j = bj - s1 < 0 ? bj - s1 + cols : bj - s1;   // map space
-    const unsigned long long w = bits[((size_t)(j / TILE) * tiles_i + i / TILE) * TILE + (j % TILE)];
-    out[k] = (uint8_t)((w >> (i % TILE)) & 1ull);
+    int i, j;
+    map_cell_of(k, rows, cols, s0, s1, i, j);
+    out[k] = fp_bit(bits, tiles_i, cols, i, j) ? 1 : 0;
   }
 }
 

@@ -17,7 +17,7 @@
 //   4. fr_init_kernel / fr_stats_kernel / fr_compact_kernel   size, bounding box, sums, ranking; the size filter
 // Every find and every union has a stated bound; a build that exceeds one sets a control word and returns RNA_ECAPACITY.
 #include "engine.hpp"
-#include "compose_dev.hpp"
+#include "map_tiles_dev.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -39,8 +39,6 @@ struct FrCtl {
 };
 
 constexpr int FR_CELLS = TILE * TILE;
-
-__device__ __forceinline__ int fr_buf(int x, int s, int n) { return x + s >= n ? x + s - n : x + s; }
 
 // ---- union-find in LDS: node ids are tile-local and ordered like the buffer indices of their cells (see the kernel) ----
 // a path visits a node once (parents are strictly smaller): at most FR_CELLS reads
@@ -126,7 +124,7 @@ __global__ void __launch_bounds__(256) fr_classify_kernel(int32_t* __restrict__ 
   for (int jj = wave; jj < TILE + 2; jj += 4) {
     const int i = i0 + lane, j = j0 - 1 + jj;
     const bool ok = i < rows && j >= 0 && j < cols;
-    const float v = master[ok ? (size_t)fr_buf(j, s1, cols) * rows + fr_buf(i, s0, rows) : 0];   // (cell 0 for lanes without a cell: read, not used)
+    const float v = master[ok ? buffer_lin(i, j, rows, cols, s0, s1) : 0];   // (cell 0 for lanes without a cell: read, not used)
     const u64 un = __ballot(ok && v != v);
     const u64 known = __ballot(ok && !(v != v));
     const u64 blk = __ballot(ok && cell_blocked(v));
@@ -134,14 +132,14 @@ __global__ void __launch_bounds__(256) fr_classify_kernel(int32_t* __restrict__ 
       unk[jj] = un;
       if (jj >= 1 && jj <= TILE) {
         const int lj = jj - 1;
-        fre[lj] = known & ~(bits ? bits[((size_t)tj * tiles_i + ti) * TILE + lj] : blk);
+        fre[lj] = known & ~(bits ? fp_bits_word(bits, tiles_i, cols, ti, j) : blk);
       }
     }
   }
   if (wave < 2) {
     const int i = wave == 0 ? i0 - 1 : i0 + TILE, j = j0 + lane;
     const bool ok = i >= 0 && i < rows && j < cols;
-    const float v = master[ok ? (size_t)fr_buf(j, s1, cols) * rows + fr_buf(i, s0, rows) : 0];
+    const float v = master[ok ? buffer_lin(i, j, rows, cols, s0, s1) : 0];
     const u64 un = __ballot(ok && v != v);
     if (lane == 0) side[wave] = un;
   }
@@ -190,9 +188,9 @@ __global__ void __launch_bounds__(256) fr_classify_kernel(int32_t* __restrict__ 
     if ((fr[lj] >> li) & 1ull) {
       const int r = fr_lds_find(parent, FR_ID(li, lj), &overflow);
       const int ri = i0 + (((r & (TILE - 1)) + wi) & (TILE - 1)), rj = j0 + (((r >> 6) + wj) & (TILE - 1));
-      out = (int32_t)(fr_buf(rj, s1, cols) * rows + fr_buf(ri, s0, rows));
+      out = buffer_lin<int>(ri, rj, rows, cols, s0, s1);
     }
-    labels[(size_t)fr_buf(j, s1, cols) * rows + fr_buf(i, s0, rows)] = out;
+    labels[buffer_lin(i, j, rows, cols, s0, s1)] = out;
   }
 #undef FR_ID
   if (wave == 0) {
@@ -218,7 +216,7 @@ __global__ void __launch_bounds__(256) fr_seam_kernel(int32_t* __restrict__ labe
   else return;
   const int i = ti * TILE + li, j = tj * TILE + lj;
   if (i >= rows || j >= cols) return;
-  const int c = fr_buf(j, s1, cols) * rows + fr_buf(i, s0, rows);
+  const int c = buffer_lin<int>(i, j, rows, cols, s0, s1);
   if (labels[c] < 0) return;
   const int tile = tj * tiles_i + ti;
   for (int dj = -1; dj <= 1; ++dj)
@@ -226,7 +224,7 @@ __global__ void __launch_bounds__(256) fr_seam_kernel(int32_t* __restrict__ labe
       const int ni = i + di, nj = j + dj;
       if ((!di && !dj) || ni < 0 || nj < 0 || ni >= rows || nj >= cols) continue;
       if ((nj >> 6) * tiles_i + (ni >> 6) <= tile) continue;
-      const int n = fr_buf(nj, s1, cols) * rows + fr_buf(ni, s0, rows);
+      const int n = buffer_lin<int>(ni, nj, rows, cols, s0, s1);
       if (__hip_atomic_load(&labels[n], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 0) continue;
       fr_union(labels, c, n, ncell, ctl);
     }
@@ -274,8 +272,8 @@ __global__ void __launch_bounds__(256) fr_stats_kernel(const int32_t* __restrict
     const bool is_fr = l >= 0;
     u64 pend = __ballot(is_fr);
     if (!pend) continue;   // (uniform)
-    const int bi = (int)(c % rows), bj = (int)(c / rows);
-    const int i = bi - s0 < 0 ? bi - s0 + rows : bi - s0, j = bj - s1 < 0 ? bj - s1 + cols : bj - s1;
+    int i, j;
+    map_cell_of(c, rows, cols, s0, s1, i, j);
     // (cost, cell) as one unsigned word, cost on top: the order of the raw int32 because a goal-field value is never negative
     // (a distance, RNA_GOAL_FIELD_FAR or RNA_GOAL_FIELD_UNREACHED)
     const u64 key = (field && is_fr) ? ((u64)(unsigned)field[c] << 32) | (unsigned)c : ~0ull;

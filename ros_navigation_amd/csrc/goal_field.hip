@@ -24,7 +24,7 @@
 // Termination is the host's: it enqueues rounds in chunks, reads the pending count back and stops at zero (rna_goal_field_build).
 // A field is a snapshot: the kernels read the live masks only during the build; paths follow the stored `next` bytes.
 #include "engine.hpp"
-#include "compose_dev.hpp"
+#include "map_tiles_dev.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -62,17 +62,11 @@ struct GfCtl {
   int passes, max_passes;   // relaxation passes over a tile in LDS: all jobs, the longest job (RNA_GOAL_FIELD_STATS)
 };
 
-__device__ __forceinline__ int gf_wrap(int v, int s, int n) { return v + s >= n ? v + s - n : v + s; }
-
 // fn + w with the 30-bit rule: a sum at or beyond 2^30 is FAR, FAR stays FAR, unreached stays unreached
 __device__ __forceinline__ int gf_add(int fn, int w) {
   const unsigned s = (unsigned)fn + (unsigned)w;
   return s < GF_LIMIT ? (int)s : (fn == GF_INF ? GF_INF : GF_FAR);
 }
-
-// neighbour k of the contract's fixed order: (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1)
-__device__ __forceinline__ int gf_di(int k) { return (int)((0x9224u >> (2 * k)) & 3u) - 1; }   // di + 1 = 0 1 2 0 2 0 1 2, two bits each
-__device__ __forceinline__ int gf_dj(int k) { return k < 3 ? -1 : (k < 5 ? 0 : 1); }
 
 // the tile's field with a one-cell halo (outside the map: unreached) -> F[GF_W rows of stride GF_S]
 __device__ __forceinline__ void gf_load_field(int* F, const int32_t* __restrict__ field, int i0, int j0, int rows, int cols, int s0,
@@ -81,7 +75,7 @@ __device__ __forceinline__ void gf_load_field(int* F, const int32_t* __restrict_
     const int ii = k % GF_W, jj = k / GF_W;
     const int i = i0 - 1 + ii, j = j0 - 1 + jj;
     int v = GF_INF;
-    if (i >= 0 && j >= 0 && i < rows && j < cols) v = field[(size_t)gf_wrap(j, s1, cols) * rows + gf_wrap(i, s0, rows)];
+    if (i >= 0 && j >= 0 && i < rows && j < cols) v = field[buffer_lin(i, j, rows, cols, s0, s1)];
     F[jj * GF_S + ii] = v;
   }
 }
@@ -92,7 +86,7 @@ __device__ __forceinline__ void gf_load_masks(uint8_t* M, uint8_t* MT, const uin
   for (int k = threadIdx.x; k < TILE * TILE; k += blockDim.x) {
     const int li = k & (TILE - 1), lj = k >> 6;
     const int i = i0 + li, j = j0 + lj;
-    const uint8_t m = (i < rows && j < cols) ? nbr[(size_t)gf_wrap(j, s1, cols) * rows + gf_wrap(i, s0, rows)] : (uint8_t)0;
+    const uint8_t m = (i < rows && j < cols) ? nbr[buffer_lin(i, j, rows, cols, s0, s1)] : (uint8_t)0;
     M[k] = m;
     MT[li * TILE + lj] = m;
   }
@@ -151,11 +145,9 @@ __global__ void gf_seed_kernel(int32_t* __restrict__ field, int* __restrict__ ke
                                int cols, int tiles_i, int s0, int s1, const float* __restrict__ master,
                                const unsigned long long* __restrict__ bits) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  const int bi = goal % rows, bj = goal / rows;
-  const int i = bi - s0 < 0 ? bi - s0 + rows : bi - s0, j = bj - s1 < 0 ? bj - s1 + cols : bj - s1;   // map space
-  bool blocked;
-  if (bits) blocked = (bits[((size_t)(j / TILE) * tiles_i + i / TILE) * TILE + (j % TILE)] >> (i % TILE)) & 1ull;
-  else blocked = cell_blocked(master[goal]);
+  int i, j;
+  map_cell_of(goal, rows, cols, s0, s1, i, j);
+  const bool blocked = bits ? fp_bit(bits, tiles_i, cols, i, j) : cell_blocked(master[goal]);
   GfCtl c = {};
   c.round[0].min_key = c.round[1].min_key = GF_INF;
   c.round[2].min_key = 0;
@@ -224,7 +216,7 @@ __global__ void __launch_bounds__(256) gf_round_kernel(int32_t* __restrict__ fie
     for (int k = threadIdx.x; k < TILE * TILE; k += blockDim.x) {
       const int pi = k & (TILE - 1), pj = k >> 6;
       const int i = i0 + pi, j = j0 + pj;
-      P[pj * GF_PS + pi] = (i < rows && j < cols) ? (uint16_t)gf_pen(clr, pen_tab, pen_r2, (size_t)gf_wrap(j, s1, cols) * rows + gf_wrap(i, s0, rows)) : (uint16_t)0;
+      P[pj * GF_PS + pi] = (i < rows && j < cols) ? (uint16_t)gf_pen(clr, pen_tab, pen_r2, buffer_lin(i, j, rows, cols, s0, s1)) : (uint16_t)0;
     }
   }
   if (threadIdx.x < 8) wake[threadIdx.x] = GF_INF;
@@ -261,7 +253,7 @@ __global__ void __launch_bounds__(256) gf_round_kernel(int32_t* __restrict__ fie
     const int lj = band + s, j = j0 + lj;
     if (i >= rows || j >= cols) continue;
     const int v = F[(lj + 1) * GF_S + li + 1];
-    int32_t* p = &field[(size_t)gf_wrap(j, s1, cols) * rows + gf_wrap(i, s0, rows)];
+    int32_t* p = &field[buffer_lin(i, j, rows, cols, s0, s1)];
     if (v < *p) {
       *p = v;
       const bool up = li == 0, dn = li == TILE - 1, lf = lj == 0, rt = lj == TILE - 1;
@@ -282,7 +274,7 @@ __global__ void __launch_bounds__(256) gf_round_kernel(int32_t* __restrict__ fie
   __syncthreads();
   if (threadIdx.x < 8) {
     const int k = threadIdx.x, v = wake[k];
-    const int a = ti + gf_di(k), b = tj + gf_dj(k);
+    const int a = ti + nbr_di(k), b = tj + nbr_dj(k);
     if (v != GF_INF && a >= 0 && b >= 0 && a < tiles_i && b < tiles_j) {
       atomicMin(&key_nxt[b * tiles_i + a], v);
       atomicMin(&cur->min_key, v);
@@ -313,7 +305,7 @@ __global__ void __launch_bounds__(256) gf_finalize_kernel(const int32_t* __restr
     const int li = k & (TILE - 1), lj = k >> 6;
     const int i = i0 + li, j = j0 + lj;
     if (i >= rows || j >= cols) continue;
-    const size_t b = (size_t)gf_wrap(j, s1, cols) * rows + gf_wrap(i, s0, rows);
+    const size_t b = buffer_lin(i, j, rows, cols, s0, s1);
     const int* c = &F[(lj + 1) * GF_S + li + 1];
     const int v = *c;
     uint8_t nx = GF_NEXT_NONE;
@@ -364,8 +356,8 @@ __global__ void __launch_bounds__(64) gf_paths_kernel(const int32_t* __restrict_
     if (f == GF_INF) r.status = 1;
     else if (f == GF_FAR) r.status = 4;
     else {
-      const int bi = s % rows, bj = s / rows;
-      int i = bi - s0 < 0 ? bi - s0 + rows : bi - s0, j = bj - s1 < 0 ? bj - s1 + cols : bj - s1;
+      int i, j;
+      map_cell_of(s, rows, cols, s0, s1, i, j);
       int32_t* out = paths + (size_t)q * max_len;
       int len = 0;   // (cells <= 2e9, rna_create)
       bool done = false, broken = false;
@@ -374,17 +366,17 @@ __global__ void __launch_bounds__(64) gf_paths_kernel(const int32_t* __restrict_
         __syncthreads();   // the previous tile's walk is over
         for (int rr = 0; rr < TILE; ++rr) {
           const int ci = i0 + lane, cj = j0 + rr;
-          T[rr * TILE + lane] = (ci < rows && cj < cols) ? next[(size_t)gf_wrap(cj, s1, cols) * rows + gf_wrap(ci, s0, rows)] : GF_NEXT_NONE;
+          T[rr * TILE + lane] = (ci < rows && cj < cols) ? next[buffer_lin(ci, cj, rows, cols, s0, s1)] : GF_NEXT_NONE;
         }
         __syncthreads();
         while ((i & ~(TILE - 1)) == i0 && (j & ~(TILE - 1)) == j0) {
-          if (len < max_len && lane == 0) out[len] = gf_wrap(j, s1, cols) * rows + gf_wrap(i, s0, rows);
+          if (len < max_len && lane == 0) out[len] = buffer_lin<int>(i, j, rows, cols, s0, s1);
           ++len;
           const int k = __builtin_amdgcn_readfirstlane((int)T[(j - j0) * TILE + (i - i0)]);
           if (k == GF_NEXT_GOAL) { done = true; break; }
           if (k > 7 || len > ncell) { broken = true; break; }   // (cannot happen for a finalized field)
-          i += gf_di(k);
-          j += gf_dj(k);
+          i += nbr_di(k);
+          j += nbr_dj(k);
           if ((unsigned)i >= (unsigned)rows || (unsigned)j >= (unsigned)cols) { broken = true; break; }
         }
       }

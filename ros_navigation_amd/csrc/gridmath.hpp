@@ -5,10 +5,13 @@
 // -ffp-contract=off so neither hipcc's host nor its gfx950 code fuses a*b+c.
 #pragma once
 
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#endif
 
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 
 namespace rna {
 
@@ -20,7 +23,11 @@ struct Geom {
   int start[2];
 };
 
+#ifdef __HIPCC__
 #define RNA_HD __host__ __device__ __forceinline__
+#else
+#define RNA_HD inline   // a host compiler alone (tests/cpp/gridmath_index_test.cpp)
+#endif
 
 // hypot() as glibc 2.35 computes it (sysdeps/ieee754/dbl-64/e_hypot.c, the non-FMA kernel: Borges' corrected
 // square root).  The reference's findNearNode / findClosedVertex compare hypot() values with a strict `<`, and on
@@ -65,6 +72,26 @@ RNA_HD void buffer_index(const Geom& g, const int u[2], int out[2]) {
   if (g.start[0] == 0 && g.start[1] == 0) { out[0] = u[0]; out[1] = u[1]; return; }
   out[0] = wrap_index(u[0] + g.start[0], g.size[0]);
   out[1] = wrap_index(u[1] + g.start[1], g.size[1]);
+}
+
+// The same two conversions, one axis, without wrap_index's divisions: an add, a compare and a conditional subtract (add).
+// PRECONDITION: 0 <= x < n (b likewise) and 0 <= s < n -- a cell of the map and the buffer's start index; then
+// map_to_buffer(x, s, n) == wrap_index(x + s, n) and buffer_to_map is its inverse.  Anything else takes wrap_index.
+RNA_HD int map_to_buffer(int x, int s, int n) { return x + s >= n ? x + s - n : x + s; }
+RNA_HD int buffer_to_map(int b, int s, int n) { return b - s < 0 ? b - s + n : b - s; }
+
+// buffer linear index (column-major layer: Index(0) fastest) of the map-space cell (i, j); same precondition per axis.
+// Lin is the caller's index type: the multiplication runs at that width (int / unsigned: the map has < 2^31 cells).
+template <class Lin = size_t>
+RNA_HD Lin buffer_lin(int i, int j, int rows, int cols, int s0, int s1) {
+  return (Lin)map_to_buffer(j, s1, cols) * (Lin)rows + (Lin)map_to_buffer(i, s0, rows);
+}
+
+// map-space (i, j) of the buffer linear index `lin`, 0 <= lin < rows * cols; the division runs at the width of Lin
+template <class Lin>
+RNA_HD void map_cell_of(Lin lin, int rows, int cols, int s0, int s1, int& i, int& j) {
+  i = buffer_to_map((int)(lin % rows), s0, rows);
+  j = buffer_to_map((int)(lin / rows), s1, cols);
 }
 
 // gmc/src/GridMapMath.cpp:146-159

@@ -9,25 +9,13 @@
 // Cost.  An anchor on an open map sees the whole rest of its path: about L^2 / 2 mask bytes per path without max_span and
 // L * max_span with it.  That is why max_span exists.
 #include "engine.hpp"
+#include "map_tiles_dev.hpp"
 
 using namespace rna;
 
 namespace {
 
 constexpr int SC_U = 8;   // line cells a lane has in flight per turn (independent loads: no address depends on a loaded value)
-
-// neighbour number of the king move (di, dj) in the contract's order (-1,-1) (0,-1) (1,-1) (-1,0) (1,0) (-1,1) (0,1) (1,1)
-__device__ __forceinline__ unsigned sc_move_bit(int di, int dj) {
-  const int k = (dj + 1) * 3 + (di + 1);
-  return 1u << (k > 4 ? k - 1 : k);
-}
-
-// buffer linear index of the map-space cell (i, j)
-__device__ __forceinline__ unsigned sc_buf(int i, int j, int rows, int cols, int s0, int s1) {
-  const int bi = i + s0 >= rows ? i + s0 - rows : i + s0;
-  const int bj = j + s1 >= cols ? j + s1 - cols : j + s1;
-  return (unsigned)bj * (unsigned)rows + (unsigned)bi;
-}
 
 __device__ __forceinline__ int sc_wave_sum(int v) {
 #pragma unroll
@@ -73,8 +61,8 @@ __global__ void __launch_bounds__(64) shortcut_kernel(const int32_t* __restrict_
   for (int t = lane; t < L; t += 64) {
     unsigned c = (unsigned)row[t];
     if ((unsigned long long)c >= ncell) { bad = true; c = 0; }
-    const int bi = (int)(c % (unsigned)rows), bj = (int)(c / (unsigned)rows);
-    const int i = bi - s0 < 0 ? bi - s0 + rows : bi - s0, j = bj - s1 < 0 ? bj - s1 + cols : bj - s1;
+    int i, j;
+    map_cell_of(c, rows, cols, s0, s1, i, j);
     P[t] = ((unsigned)j << 16) | (unsigned)i;
   }
   __syncthreads();
@@ -85,7 +73,7 @@ __global__ void __launch_bounds__(64) shortcut_kernel(const int32_t* __restrict_
       const int ai = (int)(a & 0xFFFFu), aj = (int)(a >> 16);
       const int di = (int)(b & 0xFFFFu) - ai, dj = (int)(b >> 16) - aj;
       if (di < -1 || di > 1 || dj < -1 || dj > 1 || (di == 0 && dj == 0)) bad = true;
-      else if (!(nbr[sc_buf(ai, aj, rows, cols, s0, s1)] & sc_move_bit(di, dj))) ++blocked;
+      else if (!(nbr[buffer_lin<unsigned>(ai, aj, rows, cols, s0, s1)] & nbr_move_bit(di, dj))) ++blocked;
     }
   }
   if (__any(bad)) {
@@ -107,8 +95,8 @@ __global__ void __launch_bounds__(64) shortcut_kernel(const int32_t* __restrict_
     int carry = 0;   // KEEP_CLEARANCE: min clr over p[a .. k]
     if (CLR && k < lim) {
       const unsigned p1 = P[k];
-      carry = min((int)clr[sc_buf(ai, aj, rows, cols, s0, s1)],
-                  (int)clr[sc_buf((int)(p1 & 0xFFFFu), (int)(p1 >> 16), rows, cols, s0, s1)]);
+      carry = min((int)clr[buffer_lin<unsigned>(ai, aj, rows, cols, s0, s1)],
+                  (int)clr[buffer_lin<unsigned>((int)(p1 & 0xFFFFu), (int)(p1 >> 16), rows, cols, s0, s1)]);
     }
     while (k < lim) {
       const int m = k + 1 + lane;
@@ -117,7 +105,7 @@ __global__ void __launch_bounds__(64) shortcut_kernel(const int32_t* __restrict_
       const int mi = (int)(pm & 0xFFFFu), mj = (int)(pm >> 16);
       int floor_clr = 0;   // min clr over p[a .. m]
       if (CLR) {
-        int v = valid ? (int)clr[sc_buf(mi, mj, rows, cols, s0, s1)] : RNA_CLEARANCE_NONE;
+        int v = valid ? (int)clr[buffer_lin<unsigned>(mi, mj, rows, cols, s0, s1)] : RNA_CLEARANCE_NONE;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
           const int o = __shfl_up(v, d, 64);
@@ -127,8 +115,8 @@ __global__ void __launch_bounds__(64) shortcut_kernel(const int32_t* __restrict_
       }
       const int e0[2] = {ai, aj}, e1[2] = {mi, mj};
       const IndexLine ln = index_line(e0, e1);
-      const unsigned straight = ln.major == 0 ? sc_move_bit(ln.step[0], 0) : sc_move_bit(0, ln.step[1]);
-      const unsigned diagonal = sc_move_bit(ln.step[0], ln.step[1]);
+      const unsigned straight = ln.major == 0 ? nbr_move_bit(ln.step[0], 0) : nbr_move_bit(0, ln.step[1]);
+      const unsigned diagonal = nbr_move_bit(ln.step[0], ln.step[1]);
       const int D = valid ? ln.D : 0;
       bool failed = !valid;
       int t = 0;
@@ -149,7 +137,7 @@ __global__ void __launch_bounds__(64) shortcut_kernel(const int32_t* __restrict_
             const int tt = t + u;
             const bool live = tt < D;   // cell tt has a step to test (cells past the line's last step read cell 0 and pass)
             const int ci = ai + ln.step[0] * (ln.major == 0 ? tt : cnt), cj = aj + ln.step[1] * (ln.major == 0 ? cnt : tt);
-            const unsigned c = live ? sc_buf(ci, cj, rows, cols, s0, s1) : 0u;
+            const unsigned c = live ? buffer_lin<unsigned>(ci, cj, rows, cols, s0, s1) : 0u;
             const uint8_t mk = nbr[c];
             mask[u] = live ? mk : (uint8_t)0xFF;
             if (CLR) {

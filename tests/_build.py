@@ -55,6 +55,7 @@ SOURCES = {
     "nav_node_shaped": ("tests/cpp/nav_node_shaped.cpp", "host"),
     "rate_loop_test": ("tests/cpp/rate_loop_test.cpp", "plain"),
     "id_bootstrap_test": ("tests/cpp/id_bootstrap_test.cpp", "plain"),
+    "gridmath_index_test": ("tests/cpp/gridmath_index_test.cpp", "plain"),
     "tiled_host": ("examples/tiled_host.cpp", "rccl"),
 }
 

@@ -168,20 +168,46 @@ def test_compose_after_master_was_written_directly(R):
     e.close()
 
 
-def test_update_map_compose_modes(R):
+def box_rays(rng, n, x, y, hit=0.7):
+    """n rays that start and end inside the box x = (lo, hi), y = (lo, hi): they touch no cell outside it"""
+    r = np.zeros(n, O.RAY_DTYPE)
+    r["sx"], r["sy"] = rng.uniform(x[0], x[1], n), rng.uniform(y[0], y[1], n)
+    r["ex"], r["ey"] = rng.uniform(x[0], x[1], n), rng.uniform(y[0], y[1], n)
+    r["clear_end"] = (rng.random(n) >= hit).astype(np.int32)
+    return r
+
+
+# 12.8 m x 12.8 m: 256 x 256 cells, 4 x 4 whole tiles.  7.0 m x 4.8 m: 140 x 96 cells, 3 x 2 tiles, the last tile column 12 cells
+# wide (x < -2.9), the second tile row 32 tall (y < -0.8); after a first update over the whole map, one confined to tile row 0
+# that reaches into the partial column, then one confined to tile (0, 1) of the partial row -- so the fused
+# compose-and-masks kernel, which runs from the second update on, sees some and not all of the tiles dirty.
+@pytest.mark.parametrize("lx,ly,boxes", [(12.8, 12.8, None),
+                                         (7.0, 4.8, [None, ((-3.5, -2.0), (0.0, 2.4)), ((1.0, 3.5), (-2.4, -1.0))])])
+def test_update_map_compose_modes(R, lx, ly, boxes):
     rng = np.random.default_rng(5)
     for mode in (0, 1):
-        e = R.Engine(12.8, 12.8, 0.05)  # 256 x 256 -> 4 x 4 tiles
-        g = O.make_geom(12.8, 12.8, 0.05)
+        e = R.Engine(lx, ly, 0.05)
+        g = O.make_geom(lx, ly, 0.05)
+        ti, tj = e.tile_grid()
+        some = np.zeros((tj, ti), bool)   # tiles consumed by a compose that did not consume every tile
         laser = np.full(e.ncell, np.nan, np.float32)
         for step in range(3):
-            rays = random_rays(rng, 400, 2.0 + step, outside=0.0)
+            if boxes is None or boxes[step] is None:
+                rays = random_rays(rng, 400, 2.0 + step, outside=0.0)
+            else:
+                rays = box_rays(rng, 400, *boxes[step])
             O.himm_update(g, laser, rays)
             e.update_map(rays.view(R.capi.RAY_DTYPE), compose_mode=mode)
+            dirty = e.last_dirty_tiles().reshape(tj, ti) != 0
+            if not dirty.all():
+                some |= dirty
             assert same_f32(e.download(R.capi.LAYER_LASER), laser)
             assert same_f32(e.download(R.capi.LAYER_MASTER), laser)  # master = laser (map_provider.cpp:221)
             _, nbr = O.astar_masks(laser, e.rows, e.cols)
             assert np.array_equal(e.nbr_mask(), nbr)
+        if boxes is not None and mode == 0:
+            assert (e.rows % 64, e.cols % 64) == (12, 32) and (ti, tj) == (3, 2)
+            assert some[:, -1].any() and some[-1, :].any(), some   # a tile of the partial column, a tile of the partial row
         e.close()
 
 

@@ -136,6 +136,14 @@ def test_tiled_host_id_file_bootstrap_ignores_a_stale_file():
     assert out.returncode == 0 and "id bootstrap ok" in out.stdout, out.stdout + out.stderr
 
 
+def test_gridmath_fast_index_pair_equals_wrap_index():
+    """csrc/gridmath.hpp on the host alone: map_to_buffer / buffer_to_map (one add, one compare, one conditional subtract) equal
+    wrap_index(x + s, n) and its inverse for every start and index of n in {1, 2, 63, 64, 65, 130}; buffer_lin / map_cell_of the
+    same on 130 x 70 for every start from {0, 1, 63, 64, 65, size - 1} per axis, against buffer_index / unwrap_index"""
+    out = subprocess.run([_build.cpp("gridmath_index_test")], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and "gridmath index ok" in out.stdout, out.stdout + out.stderr
+
+
 @pytest.mark.gpu
 def test_rccl_tiled_host_runs_as_a_single_rank_and_matches_the_oracle(tmp_path):
     """one rank = one GPU: ncclCommInitRank with world 1, every exchange a no-op, the rest of the loop for real -- and
