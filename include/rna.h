@@ -384,6 +384,59 @@ int rna_goal_field_paths(rna_engine* e, const int32_t* starts_host, int n, int32
 int rna_goal_field_paths_device(rna_engine* e, const int32_t* starts_device, int n, int32_t* paths_device, int max_path_len,
                                 rna_astar_result* results_device);
 
+/* ---- global planning: goal distance field with many sources, start costs and owner labels -------- */
+/* The field above with more than one seed: every robot drives to the cheapest of K docks or frontier cells (one build for the
+ * fleet), or -- the sources being the robots -- every cell learns which robot reaches it first and at what cost: the
+ * travel-cost Voronoi partition of the map.  A start cost per source is that robot's head start against it (the 12 s of work
+ * it still has).  Integers only: every output has exactly one right value.
+ *   sources   cells goals[0 .. n), buffer linear indices, and start costs seed[0 .. n), int32, 0 <= seed[k] < 2^30; a NULL
+ *             seed means all 0.  1 <= n <= cells; duplicates are allowed.  A source whose cell is in the search's blocked set
+ *             (what rna_astar_download_blocked returns: robot radius included, masks refreshed first) is skipped and counted.
+ *   field     the least fixpoint of
+ *                 field[c] = min( min over unblocked sources k with goals[k] == c of seed[k],
+ *                                 pen[c] + min over the neighbours n that c's mask allows of field[n] + w(n, c) )
+ *             w = 1000 / 1414; pen = the clearance cost when a table is set (rna_goal_field_set_clearance_cost), else 0.  A
+ *             source's own cell pays no pen on its seed term (the single goal's "the goal's own cost is not counted").  The
+ *             30-bit rule is unchanged: a sum >= 2^30 is RNA_GOAL_FIELD_FAR, and FAR propagates as itself.  Edge weights are
+ *             positive integers: the fixpoint is unique.
+ *   terminal  cell c is a terminal iff some unblocked source k has goals[k] == c and seed[k] == field[c]; a tie with an
+ *             equally cheap arrival through a neighbour goes to the terminal.  next[c] = 8 on terminals; everywhere else the
+ *             canonical rule: the first neighbour in the contract's order with field[n] + w + pen[c] == field[c].  A source
+ *             that a cheaper source undercuts is an ordinary cell.  254 / 255 as above.
+ *   owner[c]  int32 per cell, BUFFER order: the smallest k with goals[k] == t and seed[k] == field[t], t the terminal the walk
+ *             along next from c ends at; -1 on cells whose field is unreached or FAR.  The field strictly decreases along
+ *             next, so the walks form a forest and owner is unique.
+ *   paths     rna_goal_field_paths[_device] work unchanged on such a field: they walk to next == 8, cost = field[start]; a start
+ *             that is a terminal gives path_len 1 and cost = its seed; the last cell of a found path is goals[owner[start]].
+ * One source with start cost 0 gives byte for byte what rna_goal_field_build(goal) gives: field, next, reached, max_cost,
+ * tiles_reached.  info.goal = goals[0]; info.status = 2 iff every source is blocked (every cell is then unreached, the owners
+ * all -1).  Both forms return when the field -- and with RNA_GOAL_FIELD_OWNERS the labels -- is complete.  RNA_EINVAL: n < 1 or
+ * n > cells, NULL goals, unknown flag bits, a goal outside [0, cells), a seed outside [0, 2^30); the _device form cannot see
+ * its arrays before it enqueues: its seeding kernel skips and counts the bad entries, the host reads the count with the first
+ * rounds and the call then fails with RNA_EINVAL.  A failed build leaves no field (goal == -1).  RNA_ECAPACITY as above, and for
+ * an owner pass beyond its ceil(log2 cells) + 1 rounds (a defect, reported instead of a hang).
+ * The owner calls return RNA_ESTATE (the pointer is NULL) when no field is built or the field was built without the flag.
+ * Owner memory is 4 B per cell, allocated at the first build that asks for it and released with the field; rna_clone /
+ * rna_create_submap copy nothing of it.  stale, the snapshot rule and the coexistence with pipelined batches are the single
+ * goal's.  No reference counterpart. */
+#define RNA_GOAL_FIELD_OWNERS 1
+typedef struct {
+  int32_t sources;          /* n of the build; 1 for a field built by rna_goal_field_build */
+  int32_t blocked_sources;  /* skipped: their cell is in the blocked set */
+  int32_t terminals;        /* cells with next == 8 */
+  int32_t owners;           /* 1 = the owner labels were built */
+  int32_t owner_rounds;     /* global rounds of the owner pass */
+  int32_t reserved[3];      /* 0 */
+} rna_goal_field_sources_info;
+int rna_goal_field_build_multi(rna_engine* e, const int32_t* goals_host, const int32_t* seed_host /* NULL = 0 */, int n,
+                               unsigned flags, rna_goal_field_info* info_host /* may be NULL */);
+int rna_goal_field_build_multi_device(rna_engine* e, const int32_t* goals_device, const int32_t* seed_device, int n,
+                                      unsigned flags, rna_goal_field_info* info_host);
+int rna_goal_field_sources_info_get(const rna_engine* e, rna_goal_field_sources_info* out);   /* RNA_OK before a build: all 0 */
+int rna_goal_field_owners_download(rna_engine* e, int32_t* owners_host, size_t n_cells);
+void* rna_goal_field_owners_device_ptr(rna_engine* e);
+int rna_goal_field_owners_at(rna_engine* e, const int32_t* cells_host, int n, int32_t* owners_host);   /* -1 for a cell out of range */
+
 /* ---- global planning: clearance field and clearance cost (a costmap's inflation gradient) ------- */
 /* The robot radius above is a hard limit: it closes a narrow door outright and leaves every cell just outside the disc as
  * cheap as the middle of the corridor.  What costmap_2d's inflation layer adds to navfn / global_planner is the gradient:

@@ -38,6 +38,8 @@ SYMBOLS = [
     "rna_if_blocked_batch", "rna_if_blocked_batch_device",
     "rna_goal_field_build", "rna_goal_field_info_get", "rna_goal_field_download", "rna_goal_field_device_ptr",
     "rna_goal_field_paths", "rna_goal_field_paths_device",
+    "rna_goal_field_build_multi", "rna_goal_field_build_multi_device", "rna_goal_field_sources_info_get",
+    "rna_goal_field_owners_download", "rna_goal_field_owners_device_ptr", "rna_goal_field_owners_at",
     "rna_clearance_build", "rna_clearance_download", "rna_clearance_device_ptr", "rna_clearance_info_get",
     "rna_goal_field_set_clearance_cost", "rna_goal_field_get_clearance_cost",
     "rna_shortcut_paths", "rna_shortcut_paths_device", "rna_line_cells_index",
@@ -113,6 +115,10 @@ ASTAR_RESULT_DTYPE = np.dtype([("status", "<i4"), ("path_len", "<i4"), ("cost", 
 GOAL_FIELD_INFO_DTYPE = np.dtype([("goal", "<i4"), ("status", "<i4"), ("reached", "<i4"), ("max_cost", "<i4"), ("rounds", "<i4"),
                                   ("tile_jobs", "<i4"), ("tiles_reached", "<i4"), ("stale", "<i4")])
 GOAL_FIELD_UNREACHED, GOAL_FIELD_FAR = 0x7fffffff, 0x7ffffffe
+# include/rna.h rna_goal_field_sources_info and the flag of rna_goal_field_build_multi
+GOAL_FIELD_SOURCES_INFO_DTYPE = np.dtype([("sources", "<i4"), ("blocked_sources", "<i4"), ("terminals", "<i4"), ("owners", "<i4"),
+                                          ("owner_rounds", "<i4"), ("reserved", "<i4", (3,))])
+GOAL_FIELD_OWNERS = 1
 CLEARANCE_NONE = 0xFFFF   # include/rna.h RNA_CLEARANCE_NONE: no blocked cell within the clearance field's cap
 # include/rna.h rna_shortcut_result, the flag and the path-length bound of rna_shortcut_paths
 SHORTCUT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_waypoints", "<i4"), ("blocked_steps", "<i4"), ("longest_span", "<i4")])
@@ -228,6 +234,14 @@ def lib():
     L.rna_goal_field_device_ptr.restype = vp
     L.rna_goal_field_paths.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
     L.rna_goal_field_paths_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
+    if hasattr(L, "rna_goal_field_build_multi"):   # (absent only in an older build named by the developer switch RNA_LIB)
+        L.rna_goal_field_build_multi.argtypes = [vp, vp, vp, C.c_int, C.c_uint, vp]
+        L.rna_goal_field_build_multi_device.argtypes = [vp, vp, vp, C.c_int, C.c_uint, vp]
+        L.rna_goal_field_sources_info_get.argtypes = [vp, vp]
+        L.rna_goal_field_owners_download.argtypes = [vp, vp, C.c_size_t]
+        L.rna_goal_field_owners_device_ptr.argtypes = [vp]
+        L.rna_goal_field_owners_device_ptr.restype = vp
+        L.rna_goal_field_owners_at.argtypes = [vp, vp, C.c_int, vp]
     L.rna_clearance_build.argtypes = [vp, C.c_int]
     L.rna_clearance_download.argtypes = [vp, vp, C.c_size_t]
     L.rna_clearance_device_ptr.argtypes = [vp]
@@ -758,6 +772,77 @@ class Engine:
 
     def goal_field_paths_device(self, starts_ptr, n, paths_ptr, max_path_len, results_ptr):
         self._check(self._L.rna_goal_field_paths_device(self.h, starts_ptr, n, paths_ptr, max_path_len, results_ptr))
+
+    # ---- goal distance field with many sources, start costs and owner labels ----
+    def goal_field_multi(self, goals, seed=None, owners=False):
+        """Builds the field of the sources `goals` (buffer cells; duplicates allowed) with start costs `seed` (None = all 0):
+        every cell's least cost to a source (rna_goal_field_build_multi); owners=True also labels every cell with the source
+        its downhill walk ends at.  Returns the info dict (goal = goals[0]; status 2 = every source is blocked)."""
+        goals = np.ascontiguousarray(goals, np.int32).reshape(-1)
+        if seed is not None:
+            seed = np.ascontiguousarray(seed, np.int32).reshape(-1)
+            assert len(seed) == len(goals)
+        info = np.zeros(1, GOAL_FIELD_INFO_DTYPE)
+        self._check(self._L.rna_goal_field_build_multi(self.h, _ptr(goals) if len(goals) else None, None if seed is None else _ptr(seed),
+                                                       len(goals), GOAL_FIELD_OWNERS if owners else 0, _ptr(info)))
+        return self._goal_field_info(info)
+
+    def goal_field_multi_device(self, goals_ptr, seed_ptr, n, owners=False):
+        """the same from device arrays (seed_ptr None = all 0); the sources are validated on the device"""
+        info = np.zeros(1, GOAL_FIELD_INFO_DTYPE)
+        self._check(self._L.rna_goal_field_build_multi_device(self.h, goals_ptr, seed_ptr, int(n), GOAL_FIELD_OWNERS if owners else 0,
+                                                              _ptr(info)))
+        return self._goal_field_info(info)
+
+    def goal_field_sources_info(self):
+        """rna_goal_field_sources_info of the last build (all zero before one): sources, blocked_sources, terminals, owners,
+        owner_rounds"""
+        rec = np.zeros(1, GOAL_FIELD_SOURCES_INFO_DTYPE)
+        self._check(self._L.rna_goal_field_sources_info_get(self.h, _ptr(rec)))
+        return {k: int(rec[k][0]) for k in GOAL_FIELD_SOURCES_INFO_DTYPE.names if k != "reserved"}
+
+    def goal_field_owners(self):
+        """int32 per cell in buffer order: the index of the source the cell's downhill walk ends at, -1 unreached / far"""
+        a = np.empty(self.ncell, np.int32)
+        self._check(self._L.rna_goal_field_owners_download(self.h, _ptr(a), a.size))
+        return a
+
+    def goal_field_owners_ptr(self):
+        """device pointer of the owner labels (None without a field built with owners=True)"""
+        return self._L.rna_goal_field_owners_device_ptr(self.h)
+
+    def goal_field_owners_at(self, cells):
+        """the owners of a few buffer cells (-1 for a cell out of range)"""
+        cells = np.ascontiguousarray(cells, np.int32).reshape(-1)
+        out = np.full(len(cells), -1, np.int32)
+        self._check(self._L.rna_goal_field_owners_at(self.h, _ptr(cells) if len(cells) else None, len(cells),
+                                                     _ptr(out) if len(cells) else None))
+        return out
+
+    def goal_field_from_frontiers(self, min_size=1, owners=False):
+        """The field whose sources are the frontier cells of the clusters of at least min_size cells of the CURRENT frontier
+        snapshot (Engine.frontiers first), start cost 0: every robot's walk downhill ends on its nearest frontier.  The cells
+        are taken from the labels on the device (torch on the label pointer) in ascending buffer order and handed to the
+        device form.  Returns (info, source cells as a numpy array)."""
+        import torch
+        p = self.frontier_labels_ptr()
+        if not p:
+            raise RnaError("goal_field_from_frontiers: no frontier snapshot (call Engine.frontiers first)")
+        dev = self._torch_device()
+
+        class _Labels:   # the label buffer as a foreign CUDA-array-interface object: torch wraps it without a copy
+            __cuda_array_interface__ = {"shape": (self.ncell,), "typestr": "<i4", "data": (int(p), False), "version": 2}
+        labels = torch.as_tensor(_Labels(), device=dev)
+        cells = torch.nonzero(labels >= 0).reshape(-1)
+        if min_size > 1:
+            ids, inverse, counts = torch.unique(labels[cells], return_inverse=True, return_counts=True)
+            cells = cells[counts[inverse] >= int(min_size)]
+        cells = cells.to(torch.int32).contiguous()
+        if cells.numel() == 0:
+            raise RnaError("goal_field_from_frontiers: no frontier cell in a cluster of at least %d cells" % min_size)
+        torch.cuda.synchronize(dev)   # torch's stream is not the engine's
+        info = self.goal_field_multi_device(cells.data_ptr(), None, cells.numel(), owners=owners)
+        return info, cells.cpu().numpy()
 
     # ---- clearance field and the goal field's clearance cost ----
     def clearance(self, max_cells):

@@ -146,6 +146,10 @@ struct GoalField {
   int rows = 0, cols = 0, s0 = 0, s1 = 0;   // geometry the field was built with (paths are walked in its map space)
   unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
   rna_goal_field_info info{-1, 0, 0, 0, 0, 0, 0, 0};
+  // many sources (rna_goal_field_build_multi): the last build's source counts, and the owner labels when it asked for them
+  rna_goal_field_sources_info sources{0, 0, 0, 0, 0, {0, 0, 0}};
+  int32_t* owner = nullptr;        // [ncell] buffer order, allocated at the first build with RNA_GOAL_FIELD_OWNERS: index of the
+                                   // source the walk along next ends at, -1 unreached / far
   // clearance cost (rna_goal_field_set_clearance_cost): cost_n == 0 = off, the field is the plain 1000 / 1414 one
   uint16_t cost_tab[64] = {};      // entry k: cost of a free cell with k^2 <= clearance < (k + 1)^2 (entry 0 unused)
   int cost_n = 0;                  // entries (2..64): the clearance cap is cost_n - 1 cells

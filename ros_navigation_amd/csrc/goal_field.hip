@@ -6,7 +6,8 @@
 // The field is the least fixpoint of field[c] = min over the neighbours n that c's mask allows of field[n] + w(n, c) with
 // field[goal] = 0.  It is unique, so any relaxation order gives the same bits; the kernels below only decide how much
 // work is redone:
-//   gf_init_kernel / gf_seed_kernel   every cell unreached, the goal 0, the goal's tile and its ring pending
+//   gf_init_kernel / gf_seed_kernel   every cell unreached, every source its start cost (the goal 0), the sources' tiles and
+//                       their rings pending
 //   gf_round_kernel     one launch = one round: a workgroup per 64 x 64 MAP-space tile; a pending tile loads its field with
 //                       a one-cell halo and its masks into LDS, relaxes there until nothing changes, stores what fell and
 //                       posts the smallest improved value of each of its eight borders as the neighbour tile's pending key
@@ -14,8 +15,9 @@
 //                       being written in the same launch is a valid upper bound, and the neighbour's post makes the tile
 //                       run again after the launch boundary.  Tiles whose key lies `width` above the smallest pending key
 //                       are put off (the search kernel's f-buckets one level up); width 0 = every pending tile every round.
+//   gf_terminal_kernel  per source: the source whose start cost IS its cell's field value marks the cell a terminal
 //   gf_finalize_kernel  per reached tile: the canonical step of every cell (`next`, the oracle's backtrace rule run over a
-//                       field rooted at the goal), reached cells, largest distance
+//                       field rooted at the goal), reached cells, largest distance, terminals
 //   gf_paths_kernel     one wavefront per start: follows `next` tile by tile through LDS, writes the path start first
 // Clearance cost (rna_goal_field_set_clearance_cost): with a table set the fixpoint is field[c] = pen[c] + min(field[n] + w),
 // pen[c] the table's cost for c's clearance (clearance.hip) -- a non-negative integer per cell, so the least fixpoint is
@@ -23,6 +25,17 @@
 // <false> instantiations are the table-free kernels: no penalty load, no extra LDS, the same sweeps as before the table existed.
 // Termination is the host's: it enqueues rounds in chunks, reads the pending count back and stops at zero (rna_goal_field_build).
 // A field is a snapshot: the kernels read the live masks only during the build; paths follow the stored `next` bytes.
+// Many sources (rna_goal_field_build_multi): the same least fixpoint with a virtual super-source that reaches source k at
+// its start cost seed[k]; the round kernel does not know the difference.  A source cell that a cheaper arrival undercuts is an
+// ordinary cell; the others are the terminals (next == 8) the downhill walks end at.
+// Owner labels (RNA_GOAL_FIELD_OWNERS): which source the walk along `next` from a cell ends at.  `next` is a forest (the field
+// strictly decreases along it), so this is pointer jumping, in two levels:
+//   gf_owner_tile_kernel   per relaxed tile: the successors inside the tile in LDS, doubled until every cell points at the
+//                       cell of its walk that is a terminal or leaves the tile; stores the terminal's source or the first cell
+//                       outside the tile (the EXIT, encoded below -1)
+//   gf_owner_jump_kernel   global rounds: an unresolved cell takes its exit's word -- the owner when the exit is resolved, the
+//                       exit's exit otherwise: chains halve per round.  Only cells on a tile's border can be exits, so the
+//                       rounds run over those; one last launch over every cell resolves the interior.
 #include "engine.hpp"
 #include "map_tiles_dev.hpp"
 
@@ -43,6 +56,8 @@ constexpr int GF_S = GF_W + 1;            // LDS row stride (odd: lanes along i 
 constexpr uint8_t GF_NEXT_GOAL = 8, GF_NEXT_FAR = 254, GF_NEXT_NONE = 255;
 constexpr unsigned GF_DEFAULT_WIDTH = 256000;   // see gf_width(): four tiles' worth of cost; 0 / 128 k / 256 k / 512 k measured
 constexpr int GF_CHUNK = 32;              // rounds enqueued between two looks at the pending count
+constexpr int GF_OWNER_SLOTS = 36;        // jump rounds of the owner pass: ceil(log2 cells) + 1 <= 32 (cells <= 2e9)
+constexpr int GF_OWNER_CHUNK = 8;         // jump rounds enqueued between two looks at the unresolved count
 constexpr int GF_PS = TILE + 1;           // clearance cost of the tile's cells in LDS, uint16: row stride (odd, in halfwords: lanes
                                           // along j fall into distinct banks as lanes along i do)
 
@@ -60,7 +75,27 @@ struct GfCtl {
   int tile_jobs;       // tile relaxations run
   int reached, max_cost, tiles_reached;
   int passes, max_passes;   // relaxation passes over a tile in LDS: all jobs, the longest job (RNA_GOAL_FIELD_STATS)
+  int goal0;           // goals[0] as the seed kernel read it (the device form's info.goal)
+  int blocked_sources; // sources skipped: their cell is in the blocked set
+  int invalid_sources; // sources with a cell outside the map or a start cost outside [0, 2^30): the build fails
+  int terminals;       // cells with next == 8
+  int own_unres[GF_OWNER_SLOTS];   // owner pass: cells a jump round left unresolved, per round
 };
+
+// A source as the seed and the terminal kernel see it: 0 usable, 1 blocked, 2 invalid.  goals == nullptr: the one source
+// goal0 with start cost 0 (rna_goal_field_build).
+__device__ __forceinline__ int gf_source(const int32_t* __restrict__ goals, const int32_t* __restrict__ seed, int k, int goal0, int rows,
+                                         int cols, int tiles_i, int s0, int s1, const float* __restrict__ master,
+                                         const unsigned long long* __restrict__ bits, int& g, int& s, int& i, int& j) {
+  g = goals ? goals[k] : goal0;
+  s = seed ? seed[k] : 0;
+  if (g < 0 || (long long)g >= (long long)rows * cols || (unsigned)s >= GF_LIMIT) return 2;
+  map_cell_of(g, rows, cols, s0, s1, i, j);
+  return (bits ? fp_bit(bits, tiles_i, cols, i, j) : cell_blocked(master[g])) ? 1 : 0;
+}
+
+// owner words: >= 0 the source, -1 no owner (unreached, far), <= -2 unresolved: the walk goes on at buffer cell -(word + 2)
+__device__ __forceinline__ int gf_exit_word(int cell) { return -cell - 2; }
 
 // fn + w with the 30-bit rule: a sum at or beyond 2^30 is FAR, FAR stays FAR, unreached stays unreached
 __device__ __forceinline__ int gf_add(int fn, int w) {
@@ -126,43 +161,67 @@ __device__ __forceinline__ int gf_pen(const uint16_t* __restrict__ clr, const ui
 }  // namespace
 
 __global__ void gf_init_kernel(int32_t* __restrict__ field, uint8_t* __restrict__ next, size_t ncell, int* __restrict__ keys,
-                               uint8_t* __restrict__ touched, int ntile) {
+                               uint8_t* __restrict__ touched, int ntile, GfCtl* __restrict__ ctl, int32_t* __restrict__ owner) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < ncell; k += stride) {
     field[k] = GF_INF;
     next[k] = GF_NEXT_NONE;
+    if (owner) owner[k] = -1;   // (also the largest unsigned: gf_terminal_kernel takes the smallest source with atomicMin)
   }
   for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < (size_t)ntile; k += stride) {
     keys[k] = GF_INF;
     keys[ntile + k] = GF_INF;
     touched[k] = 0;
   }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    // the control words; round 0 reads slot 2: the seed kernel posts there
+    GfCtl c = {};
+    c.round[0].min_key = c.round[1].min_key = c.round[2].min_key = GF_INF;
+    c.goal0 = -1;
+    *ctl = c;
+  }
 }
 
-// one thread: the control words, and -- unless the goal cell is blocked (robot radius: the footprint's blocked set, else the
-// master layer's own predicate) -- field[goal] = 0 and the goal's tile pending for round 0
-__global__ void gf_seed_kernel(int32_t* __restrict__ field, int* __restrict__ keys, GfCtl* __restrict__ ctl, int goal, int rows,
-                               int cols, int tiles_i, int s0, int s1, const float* __restrict__ master,
-                               const unsigned long long* __restrict__ bits) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  int i, j;
-  map_cell_of(goal, rows, cols, s0, s1, i, j);
-  const bool blocked = bits ? fp_bit(bits, tiles_i, cols, i, j) : cell_blocked(master[goal]);
-  GfCtl c = {};
-  c.round[0].min_key = c.round[1].min_key = GF_INF;
-  c.round[2].min_key = 0;
-  c.round[2].pending = blocked ? 0 : 1;
-  c.status = blocked ? 2 : 0;
-  *ctl = c;
-  if (!blocked) {
-    // the goal's tile and its ring: the 0 is stored here, not by a tile job, so no job would post it to a neighbour tile
-    // when the goal lies on its tile's border (and its neighbours inside the tile are blocked)
-    field[goal] = 0;
-    const int tiles_j = (cols + TILE - 1) / TILE;
-    for (int b = j / TILE - 1; b <= j / TILE + 1; ++b)
-      for (int a = i / TILE - 1; a <= i / TILE + 1; ++a)
-        if (a >= 0 && b >= 0 && a < tiles_i && b < tiles_j) keys[b * tiles_i + a] = 0;
-  }
+// One thread per source.  A source whose cell is blocked (robot radius: the footprint's blocked set, else the master layer's
+// own predicate) or invalid is counted and skipped; every other one lowers field[goal] to its start cost and makes the goal's
+// tile and its ring pending for round 0 with that key.  Everything is a minimum: the order of the sources does not matter.
+__global__ void __launch_bounds__(256) gf_seed_kernel(int32_t* __restrict__ field, int* __restrict__ keys, GfCtl* __restrict__ ctl,
+                                                      const int32_t* __restrict__ goals, const int32_t* __restrict__ seed, int n, int goal0,
+                                                      int rows, int cols, int tiles_i, int s0, int s1, const float* __restrict__ master,
+                                                      const unsigned long long* __restrict__ bits) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  int g, s, i, j;
+  const int kind = gf_source(goals, seed, k, goal0, rows, cols, tiles_i, s0, s1, master, bits, g, s, i, j);
+  if (k == 0) ctl->goal0 = g;
+  if (kind == 2) { atomicAdd(&ctl->invalid_sources, 1); return; }
+  if (kind == 1) { atomicAdd(&ctl->blocked_sources, 1); return; }
+  // the start cost is stored here, not by a tile job, so no job would post it to a neighbour tile when the source lies on
+  // its tile's border (and its neighbours inside the tile are blocked): the ring is made pending with the same key
+  atomicMin(&field[g], s);
+  const int tiles_j = (cols + TILE - 1) / TILE;
+  for (int b = j / TILE - 1; b <= j / TILE + 1; ++b)
+    for (int a = i / TILE - 1; a <= i / TILE + 1; ++a)
+      if (a >= 0 && b >= 0 && a < tiles_i && b < tiles_j) atomicMin(&keys[b * tiles_i + a], s);
+  atomicMin(&ctl->round[2].min_key, s);
+  atomicAdd(&ctl->round[2].pending, 1);
+}
+
+// One thread per source, after the last round: source k is a terminal's source iff seed[k] == field[goals[k]] (a tie with an
+// arrival through a neighbour goes to the terminal).  The mark is the cell's `next` byte, which nothing else has written since
+// gf_init_kernel; gf_finalize_kernel keeps it.  With owner labels the cell also takes the smallest such k.
+__global__ void __launch_bounds__(256) gf_terminal_kernel(const int32_t* __restrict__ field, uint8_t* __restrict__ next,
+                                                          int32_t* __restrict__ owner, const int32_t* __restrict__ goals,
+                                                          const int32_t* __restrict__ seed, int n, int goal0, int rows, int cols, int tiles_i,
+                                                          int s0, int s1, const float* __restrict__ master,
+                                                          const unsigned long long* __restrict__ bits) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  int g, s, i, j;
+  if (gf_source(goals, seed, k, goal0, rows, cols, tiles_i, s0, s1, master, bits, g, s, i, j) != 0) return;
+  if (field[g] != s) return;
+  next[g] = GF_NEXT_GOAL;   // (every writer stores the same byte)
+  if (owner) atomicMin(reinterpret_cast<unsigned*>(&owner[g]), (unsigned)k);
 }
 
 // One relaxation round (see the head of the file).  Grid = tiles of the map in MAP space, 256 threads.  A pass over the tile
@@ -285,22 +344,23 @@ __global__ void __launch_bounds__(256) gf_round_kernel(int32_t* __restrict__ fie
 
 // The canonical step of every cell of a tile that was relaxed: the first neighbour k of the cell's mask (fixed order = lowest
 // map-space linear index first) with field[n] + w == field[c] -- oracle/astar.c's backtrace rule over a field rooted at
-// the goal.  Also the build's totals.  PEN: field[n] + w + the cell's own clearance cost == field[c].
+// the goal; a cell gf_terminal_kernel marked (its `next` byte, read before it is written) is a terminal and keeps its 8.
+// Also the build's totals.  PEN: field[n] + w + the cell's own clearance cost == field[c].
 template <bool PEN>
 __global__ void __launch_bounds__(256) gf_finalize_kernel(const int32_t* __restrict__ field, const uint8_t* __restrict__ nbr,
                                                           uint8_t* __restrict__ next, const uint8_t* __restrict__ touched,
-                                                          GfCtl* __restrict__ ctl, int goal, int rows, int cols, int s0, int s1,
+                                                          GfCtl* __restrict__ ctl, int rows, int cols, int s0, int s1,
                                                           const uint16_t* __restrict__ clr, const uint16_t* __restrict__ pen_tab, int pen_r2) {
   __shared__ int F[GF_W * GF_S];
-  __shared__ int tot[2];
+  __shared__ int tot[3];
   const int tiles_i = gridDim.x;
   const int ti = blockIdx.x, tj = blockIdx.y, t = tj * tiles_i + ti;
   if (!touched[t]) return;
   const int i0 = ti * TILE, j0 = tj * TILE;
   gf_load_field(F, field, i0, j0, rows, cols, s0, s1);
-  if (threadIdx.x < 2) tot[threadIdx.x] = 0;
+  if (threadIdx.x < 3) tot[threadIdx.x] = 0;
   __syncthreads();
-  int n_reached = 0, v_max = 0;
+  int n_reached = 0, v_max = 0, n_term = 0;
   for (int k = threadIdx.x; k < TILE * TILE; k += blockDim.x) {
     const int li = k & (TILE - 1), lj = k >> 6;
     const int i = i0 + li, j = j0 + lj;
@@ -313,7 +373,7 @@ __global__ void __launch_bounds__(256) gf_finalize_kernel(const int32_t* __restr
     else if ((unsigned)v < GF_LIMIT) {
       ++n_reached;
       v_max = max(v_max, v);
-      if ((int)b == goal) nx = GF_NEXT_GOAL;
+      if (next[b] == GF_NEXT_GOAL) { nx = GF_NEXT_GOAL; ++n_term; }
       else {
         const unsigned m = nbr[b];
         const int pen = PEN ? gf_pen(clr, pen_tab, pen_r2, b) : 0;
@@ -329,13 +389,99 @@ __global__ void __launch_bounds__(256) gf_finalize_kernel(const int32_t* __restr
   if (n_reached) {
     atomicAdd(&tot[0], n_reached);
     atomicMax(&tot[1], v_max);
+    if (n_term) atomicAdd(&tot[2], n_term);
   }
   __syncthreads();
   if (threadIdx.x == 0 && tot[0]) {
     atomicAdd(&ctl->reached, tot[0]);
     atomicMax(&ctl->max_cost, tot[1]);
     atomicAdd(&ctl->tiles_reached, 1);
+    if (tot[2]) atomicAdd(&ctl->terminals, tot[2]);
   }
+}
+
+// Owner labels, level 1.  Grid = tiles of the map in MAP space, 256 threads, a tile that was relaxed only (every other cell
+// keeps the -1 of gf_init_kernel).  P: the local index (lj * 64 + li) of a cell's successor inside the tile, or the cell itself
+// when its walk ends or leaves here: a terminal, a cell whose step leaves the tile, a cell without a step.  V: what such a
+// root stands for -- the terminal's source (left in `owner` by gf_terminal_kernel), the exit, or -1.  Pointer doubling between
+// two copies of P (a step reads one and writes the other): after s steps a pointer is 2^s successors ahead or at its root, a
+// walk inside a tile has fewer than 4096 steps, so 12 steps reach every root.  A workgroup reads and writes the `owner` words of
+// its own tile only.
+__global__ void __launch_bounds__(256) gf_owner_tile_kernel(const uint8_t* __restrict__ next, int32_t* __restrict__ owner,
+                                                            const uint8_t* __restrict__ touched, int rows, int cols, int s0, int s1) {
+  __shared__ uint16_t P[2][TILE * TILE];
+  __shared__ int V[TILE * TILE];
+  const int ti = blockIdx.x, tj = blockIdx.y, t = tj * gridDim.x + ti;
+  if (!touched[t]) return;
+  const int i0 = ti * TILE, j0 = tj * TILE;
+  for (int l = threadIdx.x; l < TILE * TILE; l += blockDim.x) {
+    const int li = l & (TILE - 1), lj = l >> 6;
+    const int i = i0 + li, j = j0 + lj;
+    int p = l, v = -1;
+    if (i < rows && j < cols) {
+      const size_t b = buffer_lin(i, j, rows, cols, s0, s1);
+      const int k = next[b];
+      if (k == GF_NEXT_GOAL) v = owner[b];
+      else if (k < 8) {
+        const int ni = li + nbr_di(k), nj = lj + nbr_dj(k);
+        if ((unsigned)ni < (unsigned)TILE && (unsigned)nj < (unsigned)TILE) p = nj * TILE + ni;
+        else v = gf_exit_word(buffer_lin<int>(i0 + ni, j0 + nj, rows, cols, s0, s1));   // (a step never leaves the map)
+      }
+    }
+    P[0][l] = (uint16_t)p;
+    V[l] = v;
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int s = 0; s < 12; ++s) {   // bound: see above
+    int changed = 0;
+    for (int l = threadIdx.x; l < TILE * TILE; l += blockDim.x) {
+      const int p = P[cur][l], q = P[cur][p];
+      P[cur ^ 1][l] = (uint16_t)q;
+      changed |= q != p;
+    }
+    cur ^= 1;
+    if (!__syncthreads_or(changed)) break;
+  }
+  for (int l = threadIdx.x; l < TILE * TILE; l += blockDim.x) {
+    const int i = i0 + (l & (TILE - 1)), j = j0 + (l >> 6);
+    if (i < rows && j < cols) owner[buffer_lin(i, j, rows, cols, s0, s1)] = V[P[cur][l]];
+  }
+}
+
+// Owner labels, level 2: one launch = one round.  An unresolved cell (word <= -2) replaces its word by its exit's word: the
+// owner when the exit is resolved, else the exit's own exit.  Every word a cell ever holds is either its walk's owner or a cell
+// farther down its walk, whichever launch it was read in -- so the word of an exit that another workgroup is replacing in the
+// same launch may be read before or after (one aligned 32-bit word, read and written whole): the result does not depend on
+// it, only how far the cell gets in this round, and that is at least as far as with the words the launch started from.  With
+// those a chain of d unresolved exits has floor(d / 2) left after a round; d < cells, so ceil(log2 cells) rounds resolve every
+// exit.  An exit is the first cell outside a tile, hence on the border of its own tile: ALL == false runs over the border cells
+// of the relaxed tiles (252 threads of the 256 have one), ALL == true over every cell once the borders are resolved -- then no
+// word that is read is written in the same launch.  Round r counts what it leaves unresolved into own_unres[r] and does
+// nothing once the round before it left nothing.
+template <bool ALL>
+__global__ void __launch_bounds__(256) gf_owner_jump_kernel(int32_t* __restrict__ owner, const uint8_t* __restrict__ touched,
+                                                            GfCtl* __restrict__ ctl, int round, int rows, int cols, int s0, int s1) {
+  const int ti = blockIdx.x, tj = blockIdx.y, t = tj * gridDim.x + ti;
+  if (!touched[t]) return;
+  if (!ALL && round > 0 && ctl->own_unres[round - 1] == 0) return;   // (written by earlier launches only)
+  const int i0 = ti * TILE, j0 = tj * TILE;
+  int left = 0;
+  for (int l = threadIdx.x; l < (ALL ? TILE * TILE : 4 * TILE - 4); l += blockDim.x) {
+    int li, lj;
+    if (ALL) { li = l & (TILE - 1); lj = l >> 6; }
+    else if (l < 2 * TILE) { li = l & (TILE - 1); lj = l < TILE ? 0 : TILE - 1; }
+    else { li = l < 3 * TILE - 2 ? 0 : TILE - 1; lj = 1 + (l - 2 * TILE) % (TILE - 2); }
+    const int i = i0 + li, j = j0 + lj;
+    if (i >= rows || j >= cols) continue;
+    int32_t* w = &owner[buffer_lin(i, j, rows, cols, s0, s1)];
+    const int v = *w;   // (only this thread writes this word)
+    if (v > -2) continue;
+    const int x = __hip_atomic_load(&owner[-v - 2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(w, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    left += x <= -2;
+  }
+  if (left) atomicAdd(&ctl->own_unres[round], left);
 }
 
 // One wavefront per start.  The walk is the same in every lane (uniform values): the lanes only share the loads of the
@@ -402,6 +548,8 @@ int goal_field_release(rna_engine* e) {
   dev_free(&f.keys);
   dev_free(&f.touched);
   dev_free(&f.pen);
+  dev_free(&f.owner);
+  f.sources = rna_goal_field_sources_info{0, 0, 0, 0, 0, {0, 0, 0}};
   f.pen_current = false;
   if (f.ctl) { (void)hipFree(f.ctl); f.ctl = nullptr; }
   if (f.ctl_host) { (void)hipHostFree(f.ctl_host); f.ctl_host = nullptr; }
@@ -441,14 +589,59 @@ unsigned gf_width() {
 
 }  // namespace
 
-extern "C" int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_info* info_host) {
-  if (!e) return RNA_EINVAL;
-  if (goal < 0 || (size_t)goal >= e->ncell) return fail(e, RNA_EINVAL, "rna_goal_field_build: goal outside the map");
-  RNA_ENTER(e);
+namespace {
+
+int gf_log2_ceil(size_t n) {
+  int k = 0;
+  while (((size_t)1 << k) < n) ++k;
+  return k;
+}
+
+// The owner pass of a finalized field (see the head of the file), on the engine stream; returns when the labels are complete.
+int gf_owners(rna_engine* e, int* rounds_out) {
+  GoalField& f = e->gfield;
+  GfCtl* ctl = static_cast<GfCtl*>(f.ctl);
+  GfCtl* host = static_cast<GfCtl*>(f.ctl_host);
+  const dim3 grid(e->tiles_i, e->tiles_j), block(256);
+  hipLaunchKernelGGL(gf_owner_tile_kernel, grid, block, 0, e->stream, f.next, f.owner, f.touched, f.rows, f.cols, f.s0, f.s1);
+  // border rounds in chunks until one leaves nothing unresolved: at most ceil(log2 cells) of them (gf_owner_jump_kernel)
+  const int cap = std::max(1, gf_log2_ceil(e->ncell));
+  int round = 0, clean = -1;
+  while (clean < 0) {
+    for (int k = 0; k < GF_OWNER_CHUNK && round < cap; ++k, ++round)
+      hipLaunchKernelGGL(gf_owner_jump_kernel<false>, grid, block, 0, e->stream, f.owner, f.touched, ctl, round, f.rows, f.cols, f.s0, f.s1);
+    RNA_HIP(e, hipGetLastError());
+    RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
+    RNA_HIP(e, hipStreamSynchronize(e->stream));
+    for (int r = 0; r < round && clean < 0; ++r)
+      if (host->own_unres[r] == 0) clean = r;
+    if (clean < 0 && round >= cap)
+      return fail(e, RNA_ECAPACITY, "rna_goal_field_build_multi: the owner pass did not settle within its bound (" + std::to_string(round) +
+                                        " rounds)");
+  }
+  // the gather: every cell, its count goes into the slot behind the border rounds
+  const int slot = GF_OWNER_SLOTS - 1;
+  hipLaunchKernelGGL(gf_owner_jump_kernel<true>, grid, block, 0, e->stream, f.owner, f.touched, ctl, slot, f.rows, f.cols, f.s0, f.s1);
+  RNA_HIP(e, hipGetLastError());
+  RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
+  RNA_HIP(e, hipStreamSynchronize(e->stream));
+  if (host->own_unres[slot] != 0)
+    return fail(e, RNA_ECAPACITY, "rna_goal_field_build_multi: the owner pass left " + std::to_string(host->own_unres[slot]) +
+                                      " cells unresolved");
+  *rounds_out = clean + 2;   // the border rounds up to the first clean one, and the gather
+  return RNA_OK;
+}
+
+// The build behind both entry points.  goals / seed: DEVICE arrays of n sources (seed may be NULL = all 0), or goals == NULL:
+// the one source goal0 with start cost 0.  checked: the host has validated the sources already.
+int gf_build(rna_engine* e, const int32_t* goals, const int32_t* seed, int n, int32_t goal0, unsigned flags, rna_goal_field_info* info_host,
+             const char* who) {
   int rc = map_prepare_nbr(e);
   if (rc != RNA_OK) return rc;
   if ((rc = gf_alloc(e)) != RNA_OK) return rc;
   GoalField& f = e->gfield;
+  const bool owners = (flags & RNA_GOAL_FIELD_OWNERS) != 0;
+  if (owners && !f.owner && (rc = dev_alloc(e, &f.owner, e->ncell)) != RNA_OK) return rc;
   // clearance cost: a clearance field of the table's cap for the current masks, and the table by squared clearance
   const bool pen = f.cost_n > 0;
   const int pen_r = f.cost_n - 1, pen_r2 = pen_r * pen_r;
@@ -471,19 +664,25 @@ extern "C" int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_
   // (no field while this one is being built, also when the build fails from here on; a failure above -- the clearance
   // refresh, the table upload -- leaves the previous field in place: its buffers have not been touched yet)
   f.info.goal = -1;
+  f.sources = rna_goal_field_sources_info{0, 0, 0, 0, 0, {0, 0, 0}};
   GfCtl* ctl = static_cast<GfCtl*>(f.ctl);
   GfCtl* host = static_cast<GfCtl*>(f.ctl_host);
+  const float* master = e->layer[RNA_LAYER_MASTER];
+  const unsigned long long* bits = e->robot_r > 0.0 ? e->fp_bits : (const unsigned long long*)nullptr;
+  const dim3 per_source((unsigned)((n + 255) / 256));
   hipLaunchKernelGGL(gf_init_kernel, dim3((unsigned)std::min<size_t>((e->ncell + 255) / 256, 8192)), dim3(256), 0, e->stream, f.field,
-                     f.next, e->ncell, f.keys, f.touched, ntile);
-  hipLaunchKernelGGL(gf_seed_kernel, dim3(1), dim3(1), 0, e->stream, f.field, f.keys, ctl, goal, rows, cols, e->tiles_i, s0, s1,
-                     e->layer[RNA_LAYER_MASTER], e->robot_r > 0.0 ? e->fp_bits : (const unsigned long long*)nullptr);
+                     f.next, e->ncell, f.keys, f.touched, ntile, ctl, owners ? f.owner : (int32_t*)nullptr);
+  hipLaunchKernelGGL(gf_seed_kernel, per_source, dim3(256), 0, e->stream, f.field, f.keys, ctl, goals, seed, n, goal0, rows, cols,
+                     e->tiles_i, s0, s1, master, bits);
   RNA_HIP(e, hipGetLastError());
   // Rounds in chunks; the pending count decides between them.  Hard caps, from true bounds: a
   // shortest path crosses tile borders at most once per border cell, fewer than 128 x tiles times, and after k plain rounds
-  // every cell whose path has <= k crossings is final; with a width the smallest pending key grows by >= 1000 a round and no
-  // finite distance exceeds 1414 x cells.  More rounds than that, or 30 s, is a bug in the kernel: an error, not a hang.
+  // every cell whose path has <= k crossings is final; with a width the smallest pending key grows by >= 1000 a round and the
+  // finite distances of a connected component lie within 1414 x its cells of its cheapest source: 1414 x cells over all of
+  // them, and one round per source for the gaps between them.  More rounds than that, or 30 s, is a bug in the kernel: an
+  // error, not a hang.
   const unsigned width = gf_width();
-  const long long cap = width ? (long long)(1.5 * (double)e->ncell) + 64 : 128ll * ntile + 64;
+  const long long cap = (width ? (long long)(1.5 * (double)e->ncell) + 64 : 128ll * ntile + 64) + (n - 1);
   const auto t0 = std::chrono::steady_clock::now();
   long long round = 0;
   for (;;) {
@@ -494,14 +693,20 @@ extern "C" int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_
     RNA_HIP(e, hipGetLastError());
     RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
     RNA_HIP(e, hipStreamSynchronize(e->stream));
+    // (the device form's sources are seen here first: the seed kernel skipped the bad ones, the field is dropped)
+    if (host->invalid_sources)
+      return fail(e, RNA_EINVAL, std::string(who) + ": " + std::to_string(host->invalid_sources) +
+                                     " sources with a cell outside the map or a start cost outside [0, 2^30)");
     if (host->round[(round + 2) % 3].pending == 0) break;
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (round > cap || secs > 30.0)
-      return fail(e, RNA_ECAPACITY, "rna_goal_field_build: the relaxation did not settle within its bound (" + std::to_string(round) +
+      return fail(e, RNA_ECAPACITY, std::string(who) + ": the relaxation did not settle within its bound (" + std::to_string(round) +
                                         " rounds, " + std::to_string(secs) + " s)");
   }
+  hipLaunchKernelGGL(gf_terminal_kernel, per_source, dim3(256), 0, e->stream, f.field, f.next, owners ? f.owner : (int32_t*)nullptr, goals,
+                     seed, n, goal0, rows, cols, e->tiles_i, s0, s1, master, bits);
   hipLaunchKernelGGL(pen ? gf_finalize_kernel<true> : gf_finalize_kernel<false>, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream,
-                     f.field, e->nbr, f.next, f.touched, ctl, goal, rows, cols, s0, s1, pen ? e->clearance.clr : (const uint16_t*)nullptr,
+                     f.field, e->nbr, f.next, f.touched, ctl, rows, cols, s0, s1, pen ? e->clearance.clr : (const uint16_t*)nullptr,
                      f.pen, pen_r2);
   RNA_HIP(e, hipGetLastError());
   RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
@@ -512,8 +717,100 @@ extern "C" int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_
   if (getenv("RNA_GOAL_FIELD_STATS"))   // developer knob
     fprintf(stderr, "[goal field] width %u: %d rounds, %d tile jobs on %d tiles, %d passes (longest job %d)\n", width, host->rounds,
             host->tile_jobs, host->tiles_reached, host->passes, host->max_passes);
-  f.info = rna_goal_field_info{goal, host->status, host->reached, host->max_cost, host->rounds, host->tile_jobs, host->tiles_reached, 0};
+  // (the pass below overwrites the pinned copy)
+  const rna_goal_field_info info = {host->goal0, host->blocked_sources == n ? 2 : 0, host->reached, host->max_cost, host->rounds,
+                                    host->tile_jobs, host->tiles_reached, 0};
+  rna_goal_field_sources_info src = {n, host->blocked_sources, host->terminals, owners ? 1 : 0, 0, {0, 0, 0}};
+  // (every source blocked: nothing was relaxed, the labels are the -1 of gf_init_kernel)
+  if (owners && info.status == 0 && (rc = gf_owners(e, &src.owner_rounds)) != RNA_OK) return rc;
+  f.info = info;
+  f.sources = src;
   if (info_host) *info_host = f.info;
+  return RNA_OK;
+}
+
+int gf_owners_ready(rna_engine* e, const char* who) {
+  if (e->gfield.info.goal < 0) return fail(e, RNA_ESTATE, std::string(who) + ": no field has been built");
+  if (!e->gfield.sources.owners) return fail(e, RNA_ESTATE, std::string(who) + ": the field was built without RNA_GOAL_FIELD_OWNERS");
+  return RNA_OK;
+}
+
+}  // namespace
+
+extern "C" int rna_goal_field_build(rna_engine* e, int32_t goal, rna_goal_field_info* info_host) {
+  if (!e) return RNA_EINVAL;
+  if (goal < 0 || (size_t)goal >= e->ncell) return fail(e, RNA_EINVAL, "rna_goal_field_build: goal outside the map");
+  RNA_ENTER(e);
+  return gf_build(e, nullptr, nullptr, 1, goal, 0u, info_host, "rna_goal_field_build");
+}
+
+extern "C" int rna_goal_field_build_multi_device(rna_engine* e, const int32_t* goals_device, const int32_t* seed_device, int n,
+                                                 unsigned flags, rna_goal_field_info* info_host) {
+  if (!e) return RNA_EINVAL;
+  if (n < 1 || (size_t)n > e->ncell || !goals_device || (flags & ~(unsigned)RNA_GOAL_FIELD_OWNERS))
+    return fail(e, RNA_EINVAL, "rna_goal_field_build_multi_device: n outside 1..cells, NULL goals or unknown flag bits");
+  RNA_ENTER(e);
+  return gf_build(e, goals_device, seed_device, n, -1, flags, info_host, "rna_goal_field_build_multi_device");
+}
+
+extern "C" int rna_goal_field_build_multi(rna_engine* e, const int32_t* goals_host, const int32_t* seed_host, int n, unsigned flags,
+                                          rna_goal_field_info* info_host) {
+  if (!e) return RNA_EINVAL;
+  if (n < 1 || (size_t)n > e->ncell || !goals_host || (flags & ~(unsigned)RNA_GOAL_FIELD_OWNERS))
+    return fail(e, RNA_EINVAL, "rna_goal_field_build_multi: n outside 1..cells, NULL goals or unknown flag bits");
+  for (int k = 0; k < n; ++k) {
+    if (goals_host[k] < 0 || (size_t)goals_host[k] >= e->ncell) return fail(e, RNA_EINVAL, "rna_goal_field_build_multi: goal outside the map");
+    if (seed_host && (seed_host[k] < 0 || seed_host[k] >= (1 << 30)))
+      return fail(e, RNA_EINVAL, "rna_goal_field_build_multi: start cost outside [0, 2^30)");
+  }
+  RNA_ENTER(e);
+  int32_t *d_goals = nullptr, *d_seed = nullptr;
+  hipError_t err = hipMalloc(&d_goals, (size_t)n * sizeof(int32_t));
+  if (err == hipSuccess && seed_host) err = hipMalloc(&d_seed, (size_t)n * sizeof(int32_t));
+  if (err == hipSuccess) err = hipMemcpyAsync(d_goals, goals_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+  if (err == hipSuccess && seed_host) err = hipMemcpyAsync(d_seed, seed_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+  // (pageable host memory: the copies have left the caller's arrays when the calls return; the build ends with the stream idle)
+  const int rc = err == hipSuccess ? gf_build(e, d_goals, d_seed, n, -1, flags, info_host, "rna_goal_field_build_multi") : RNA_OK;
+  if (rc != RNA_OK) (void)hipStreamSynchronize(e->stream);   // a failed build may have left kernels behind that read the arrays
+  if (d_goals) (void)hipFree(d_goals);
+  if (d_seed) (void)hipFree(d_seed);
+  RNA_HIP(e, err);
+  return rc;
+}
+
+extern "C" int rna_goal_field_sources_info_get(const rna_engine* e, rna_goal_field_sources_info* out) {
+  if (!e || !out) return RNA_EINVAL;
+  *out = e->gfield.sources;
+  return RNA_OK;
+}
+
+extern "C" int rna_goal_field_owners_download(rna_engine* e, int32_t* owners_host, size_t n_cells) {
+  if (!e || !owners_host || n_cells != e->ncell) return RNA_EINVAL;
+  const int rc = gf_owners_ready(e, "rna_goal_field_owners_download");
+  if (rc != RNA_OK) return rc;
+  RNA_ENTER_NOJOIN(e);
+  RNA_HIP(e, hipMemcpyAsync(owners_host, e->gfield.owner, n_cells * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  RNA_HIP(e, hipStreamSynchronize(e->stream));
+  return RNA_OK;
+}
+
+extern "C" void* rna_goal_field_owners_device_ptr(rna_engine* e) {
+  return (e && e->gfield.info.goal >= 0 && e->gfield.sources.owners) ? (void*)e->gfield.owner : nullptr;
+}
+
+extern "C" int rna_goal_field_owners_at(rna_engine* e, const int32_t* cells_host, int n, int32_t* owners_host) {
+  if (!e || n < 0 || (n > 0 && (!cells_host || !owners_host))) return RNA_EINVAL;
+  const int rc = gf_owners_ready(e, "rna_goal_field_owners_at");
+  if (rc != RNA_OK) return rc;
+  if (n == 0) return RNA_OK;
+  RNA_ENTER_NOJOIN(e);
+  // a few cells (the frontier records' nearest cells): one word each, no kernel
+  for (int k = 0; k < n; ++k) {
+    owners_host[k] = -1;
+    if (cells_host[k] >= 0 && (size_t)cells_host[k] < e->ncell)
+      RNA_HIP(e, hipMemcpyAsync(&owners_host[k], e->gfield.owner + cells_host[k], sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  }
+  RNA_HIP(e, hipStreamSynchronize(e->stream));
   return RNA_OK;
 }
 

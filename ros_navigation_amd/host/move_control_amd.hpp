@@ -744,6 +744,17 @@ class GridGoalField {
     setClearanceCost(clearance_cost);
     if (!rebuild() && info_.goal < 0) throw std::runtime_error("GridGoalField: goal outside the map");
   }
+  // Many goals (rna_goal_field_build_multi): the field is every cell's least cost to ONE of them, `seed` (empty = all 0, else
+  // one entry per goal, 0 <= seed < 2^30) the cost a plan to that goal starts with; makePlan ends at the cheapest goal.  With
+  // owners the map is also partitioned by the goal each cell's plan ends at (ownerOf, assignFrontiers): goals = the robots of
+  // a fleet and seed = the work each still has gives "which robot takes which frontier".  std::runtime_error when a goal is
+  // outside the map, seed has another length or the build fails.
+  GridGoalField(GridMap& map, const std::vector<Position>& goals, const std::vector<int32_t>& seed = std::vector<int32_t>(),
+                bool owners = false)
+      : map_(map), goal_(goals.empty() ? Position(0.0, 0.0) : goals[0]), multi_(true), goals_(goals), seed_(seed), owners_(owners) {
+    if (goals.empty() || (!seed.empty() && seed.size() != goals.size())) throw std::invalid_argument("GridGoalField: goals / seed");
+    if (!rebuild() && info_.goal < 0) throw std::runtime_error("GridGoalField: goal outside the map");
+  }
   // entry k (1 .. size - 1): cost in A* cost units of a free cell k cells (rounded down) from the nearest obstacle; an empty
   // table turns the cost off.  The field that is there turns stale(); rebuild() applies the table.
   void setClearanceCost(const std::vector<uint16_t>& table) {
@@ -758,11 +769,43 @@ class GridGoalField {
     return t;
   }
   // false when the goal is outside the map (the old field stays) or its cell is blocked (every start is then unreached)
+  // (many goals: false when one of them is outside the map, or every one of them is blocked)
   bool rebuild() {
     grid_map::Index g;
+    if (multi_) {
+      std::vector<int32_t> cells(goals_.size());
+      for (size_t k = 0; k < goals_.size(); ++k) {
+        Position p = goals_[k];
+        if (!map_.getIndex(p, g)) return false;
+        cells[k] = g[0] + g[1] * map_.getSize()[0];
+      }
+      grid_map::rna_check(rna_goal_field_build_multi(map_.engine(), cells.data(), seed_.empty() ? nullptr : seed_.data(), (int)cells.size(),
+                                                     owners_ ? RNA_GOAL_FIELD_OWNERS : 0u, &info_),
+                          map_.engine(), "GridGoalField::rebuild");
+      return info_.status == 0;
+    }
     if (!map_.getIndex(goal_, g)) return false;
     grid_map::rna_check(rna_goal_field_build(map_.engine(), g[0] + g[1] * map_.getSize()[0], &info_), map_.engine(), "GridGoalField::rebuild");
     return info_.status == 0;
+  }
+  // index into the constructor's goals of the goal a plan from `p` ends at; -1 when p is outside the map or cannot reach one.
+  // std::runtime_error for a field built without owners.
+  int ownerOf(Position& p) {
+    grid_map::Index c;
+    if (!map_.getIndex(p, c)) return -1;
+    const int32_t cell = c[0] + c[1] * map_.getSize()[0];
+    int32_t owner = -1;
+    grid_map::rna_check(rna_goal_field_owners_at(map_.engine(), &cell, 1, &owner), map_.engine(), "GridGoalField::ownerOf");
+    return owner;
+  }
+  // the owner of every record's `nearest` cell: with the goals = the robots, the robot that reaches that frontier first
+  std::vector<int> assignFrontiers(const std::vector<Frontier>& frontiers) {
+    const int rows = map_.getSize()[0];
+    std::vector<int32_t> cells(frontiers.size()), owner(frontiers.size(), -1);
+    for (size_t k = 0; k < frontiers.size(); ++k) cells[k] = frontiers[k].nearest[0] + frontiers[k].nearest[1] * rows;
+    grid_map::rna_check(rna_goal_field_owners_at(map_.engine(), cells.data(), (int)cells.size(), owner.data()), map_.engine(),
+                        "GridGoalField::assignFrontiers");
+    return std::vector<int>(owner.begin(), owner.end());
   }
   bool stale() const {
     rna_goal_field_info i;
@@ -833,6 +876,10 @@ class GridGoalField {
   rna_goal_field_info info_ = {-1, 0, 0, 0, 0, 0, 0, 0};
   bool shortcut_ = false, shortcut_clearance_ = false;
   int shortcut_span_ = 0;
+  bool multi_ = false;   // built from many goals
+  std::vector<Position> goals_;
+  std::vector<int32_t> seed_;
+  bool owners_ = false;
 };
 
 // RrtPlanner(GridMap&, start, target, closeTolerance).makePlan(path) (rrt_planner.h:17-28): clears
