@@ -325,7 +325,11 @@ int rna_astar_download_nbr_mask(rna_engine* e, uint8_t* host, size_t n_cells);
  * of DESIGN.md's grid A* contract; a start or goal in the inflated region answers as a blocked one.  Valid:
  * 0 <= r and r / resolution <= 63, anything else is RNA_EINVAL.  Batches already issued keep the masks they were
  * issued with; the next batch (or rna_astar_download_nbr_mask) sees the new radius.  rna_clone and rna_create_submap
- * copy it. */
+ * copy it.  The blocked set is a function of the master layer AND of the geometry, start index included: where the box
+ * of a disc ends exactly on the map's far edge (radii of k + 1/2 cells) the iterator's corner index equals the size, which
+ * the reference wraps to 0 on a moved buffer and leaves out of range on an unmoved one, so the same map in map order
+ * can block a few cells of the rows next to that edge on a moved buffer that it leaves free on an unmoved one.  Both
+ * answers are the reference's, and the engine gives the one of its own start index. */
 int rna_astar_set_robot_radius(rna_engine* e, double radius);
 int rna_astar_get_robot_radius(const rna_engine* e, double* radius);
 /* the blocked set the search uses (rows*cols uint8 in buffer order, 1 = blocked), refreshed first as
@@ -357,7 +361,9 @@ int rna_if_blocked_batch_device(rna_engine* e, const double* xy_device, int n, d
  *             max_path_len (path_len = true length), 4 far; expanded = rounds = buckets = 0.
  * A field is a SNAPSHOT: map updates, rna_move or a new robot radius after the build change neither the field nor the paths
  * drawn from it; info.stale turns 1 once a call that can change the masks has run (any HIMM batch, compose, upload, fill,
- * unpack, rna_layer_device_ptr, move or radius call -- conservative), and the next rna_goal_field_build refreshes it.
+ * unpack, rna_layer_device_ptr, move or radius call -- conservative: also a call that changes nothing, such as rna_move to
+ * the current position, the radius it already has, HIMM on the range layer; stale is never 0 after a change and may be 1
+ * after none), and the next rna_goal_field_build refreshes it.
  * Memory (5 B per cell) is allocated at the first build; rna_clone / rna_create_submap do not copy a field. */
 #define RNA_GOAL_FIELD_UNREACHED 0x7fffffff
 #define RNA_GOAL_FIELD_FAR       0x7ffffffe

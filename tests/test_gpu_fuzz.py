@@ -3,7 +3,8 @@ hours) with a FIXED seed and a short budget each, as subprocesses -- random map 
 64 x 16 search tiles, densities 0..0.6, unknown cells, bucket widths 2828..400000, chunked batches, engine reuse, maps
 moved once or twice (grid A*); random geometry / resolution / moved buffers, end points on cell centres, edges and the
 map border, poses past the border (map update + VFH+); resolutions 0.025-0.2 m, origins up to 2000 m, radii of k and k + 1/2
-cells, moved maps (robot radius).  A fuzzer exits non-zero at the first difference from the oracle
+cells, moved maps (robot radius); sequences of map operations on one engine against the model of tests/_mapmodel.py (map state).
+A fuzzer exits non-zero at the first difference from the oracle
 and prints the configuration that reproduces it.  The search kernel's correctness rests on an asynchronous scheduler,
 `asm volatile` fences and on what the optimiser may hoist: this net catches what the hand-picked cases do not."""
 import os
@@ -42,3 +43,11 @@ def test_fuzz_footprint_fixed_seed():
     # by the oracle's own so that only the oracle side runs: 25 maps in 10 s with this seed (16 and 24 with seeds 1 and 2).
     # The floor is below half of that, because the GPU host's CPUs are shared.
     assert maps >= 8, text
+
+
+def test_fuzz_map_sequences_fixed_seed():
+    text = run_fuzzer("fuzz_map_sequences.py", 10, 306)
+    sequences = int(text.split("fuzz ok:")[1].split("sequences")[0])
+    # 12 sequences in 10 s with this seed on an MI355X host (DESIGN.md section 4 has the per-test times), most of it the oracles in
+    # Python; the floor is far below that because the GPU host's CPUs are shared.
+    assert sequences >= 2, text
