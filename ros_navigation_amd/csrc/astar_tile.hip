@@ -439,7 +439,9 @@ struct TsaLocalSched {
       uint4 h;   // classes 4 lane .. 4 lane + 3
       {
         typedef unsigned v4u __attribute__((ext_vector_type(4)));
-        const v4u hv4 = *reinterpret_cast<const volatile v4u*>(&head_[4 * lane]);
+        // (read through an LDS pointer: through the generic one this volatile read was a flat_load_dwordx4 whose 64-bit lane address
+        // lived in two VGPRs of the kernel, in scratch during a tile job and reloaded from there after every job)
+        const v4u hv4 = *(const volatile __attribute__((address_space(3))) v4u*)(&head_[4 * lane]);
         h = make_uint4(hv4.x, hv4.y, hv4.z, hv4.w);
       }
       const bool e0 = (h.x & 0xffffu) != 0xffffu, e1 = (h.y & 0xffffu) != 0xffffu, e2 = (h.z & 0xffffu) != 0xffffu, e3 = (h.w & 0xffffu) != 0xffffu;
@@ -881,7 +883,22 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
     // what each cell may pass on in this bucket: sixteen rows, no branches (also on a sticky turn: kept across the turns, the
     // sixteen values were live through the page look-ups and the halo step, and the kernel spilled into scratch -- whose
     // loads wait for every store in flight; a turn that finds nothing has left before this point anyway)
-#define TSA_APPLY_PP(b) TSA_PP(b) = TSA_G(b) >= TSA_HT(b) ? TSA_G(b) : 0;
+    // (h + thr of a row as ONE block of assembly here, its scalar |dy| a temporary of the block: as sixteen TSA_HT the sixteen
+    // s_absdiff_i32 were scheduled ahead of the rows and their results, with the sixteen products 414 dy, held thirty scalar
+    // registers across the step -- the registers whose contents were spilled before it and reloaded after it in every working job)
+#define TSA_APPLY_PP(b)                                                                                          \
+  {                                                                                                              \
+    int dy_, ht_;                                                                                                \
+    asm volatile("s_absdiff_i32 %[dy], %[jg], %[nb]\n\t"                                                         \
+                 "v_max_i32 %[h], %[dy], %[dxl]\n\t"                                                             \
+                 "s_mulk_i32 %[dy], %[c414]\n\t"                                                                 \
+                 "v_mad_u32_u24 %[h], %[h], %[c586], %[dx414]\n\t"                                               \
+                 "v_add_u32 %[h], %[dy], %[h]"                                                                   \
+                 : [dy] "=&s"(dy_), [h] "=&v"(ht_)                                                               \
+                 : [jg] "s"(jg), [nb] "n"(-(b)), [dxl] "v"(dxl), [c414] "n"(COST_D - COST_S), [c586] "s"(2 * COST_S - COST_D), [dx414] "v"(dx414) \
+                 : "scc");                                                                                       \
+    TSA_PP(b) = TSA_G(b) >= ht_ ? TSA_G(b) : 0;                                                                  \
+  }
     TSA_R16(TSA_APPLY_PP)
 #undef TSA_APPLY_PP
     // the rows the halo changed, as whole words: each is evaluated in the first sweep (its own horizontal steps) and
@@ -966,8 +983,7 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
       TSA_PP(b) = TSA_G(b) >= ht_ ? TSA_G(b) : 0;                                                                \
       /* the passes along the row, hand-scheduled: 8 vector + 4 scalar instructions per pass that moves something, 5 + 1 \
          for the last one (the compiler's version of this loop spent 7 scalar instructions and two s_nop per pass on the    \
-         loop control).  `left_` holds one bit per pass still allowed.  ([ag] and [bit] are dead operands: removing them changes  \
-         the kernel's instruction stream, so they go with the next change that is measured on a GPU.) */                      \
+         loop control).  `left_` holds one bit per pass still allowed. */                                                      \
       unsigned left_ = 1u << (TSA_HPASS - 1);                                                                  \
       {                                                                                                          \
         int t1_, t2_;                                                                                            \
@@ -988,9 +1004,9 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
             "s_lshr_b32 %[left], %[left], 1\n\t"                                                                  \
             "s_cbranch_scc1 .Lhp_top%=\n\t"                                                                       \
             ".Lhp_done%=:"                                                                                        \
-            : [g] "+v"(TSA_G(b)), [pp] "+v"(TSA_PP(b)), [all] "+s"(up_), [left] "+s"(left_), [ag] "+s"(AGVAR),    \
+            : [g] "+v"(TSA_G(b)), [pp] "+v"(TSA_PP(b)), [all] "+s"(up_), [left] "+s"(left_),                       \
               [t1] "=&v"(t1_), [t2] "=&v"(t2_)                                                                   \
-            : [nS] "v"(nS), [open] "v"(open_), [ht] "v"(ht_), [bit] "n"(b)                                       \
+            : [nS] "v"(nS), [open] "v"(open_), [ht] "v"(ht_)                                                     \
             : "vcc", "scc");                                                                                     \
       }                                                                                                          \
       TSA_STAT_HP(left_);                                                                                        \
@@ -1151,11 +1167,9 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
     // (Rejected: reading the neighbours' edges again here, in every job or only for the sides about to wake -- fewer jobs that
     // find nothing, but -1.0 % / -2.4 % on the bench: docs/history.md "Search kernel variants that were built and rejected",
     // profiles/r05_ab_fresh_wake_tests.txt, profiles/r06_ab_confirm.txt.)
-    // (the order of these three declarations is an accident the instruction stream depends on: any other order compiles to
-    // the same code with other scalar registers.  Free to change with the next change that is measured on a GPU.)
+    const bool col_any = (qany & 1ull) || (qany >> 63) || (q0 & 1ull) || (q0 >> 63) || (q15 & 1ull) || (q15 >> 63);
     bool wakeN = q0 != 0ull, wakeS = q15 != 0ull;
     int kfN = 0, kfS = 0, kfW = 0, kfE = 0;
-    const bool col_any = (qany & 1ull) || (qany >> 63) || (q0 & 1ull) || (q0 >> 63) || (q15 & 1ull) || (q15 >> 63);
     if (wakeN) {
       const int topv = (int)scr[84 + lane];
       const int c_ = __builtin_amdgcn_inverse_ballot_w64(q0) ? g0 : 0;
@@ -1617,6 +1631,9 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
       TSA_CNT(7, 1);
       tsa_job(sch, s_scr[wv], lane, t, C, first, bucket_end_u, key_base, key_shift, &spare TSA_ACC_ARG);
       // (the tile has been released by the job itself -- or kept for further turns while wake-ups kept coming: TsaLocalSched::finish)
+      // (both flags are false whenever a job is taken; said here, they are not two lane masks kept -- spilled -- across the job)
+      idle = false;
+      open_blocked = false;
     }
     // ---- the bucket is at its fixed point (or the search is being abandoned) ----
     __syncthreads();
