@@ -22,8 +22,9 @@
 // offers it), free wavefronts take the tile with the lowest key, and an f-bucket is at its fixed point when every
 // wavefront of the workgroup is idle (TsaLocalSched below).
 // Pages are handed out by the job that first changes a tile; every query slot owns a contiguous run of `cap` + 1 pages and
-// a tile -> page table (tmap), so the 2-4 % of the map a search visits sits in a few MiB of HBM, and the workgroup that
-// takes the slot next resets exactly the pages that were handed out.  Local page 0 of a slot is never written and always
+// a tile -> page table (tmap), so the 2-4 % of the map a search visits sits in a few MiB of HBM.  A page is reached through the
+// table only; the job that hands it out writes it whole before it enters it, so the workgroup that takes the slot next resets
+// the table entries that were made and leaves the pages alone.  Local page 0 of a slot is never written and always
 // "unreached": reads of tiles without a page go there.
 // Exactness: every update is a max over (KU - length) of real paths, every improvement that can matter to a neighbour
 // sets its wake-up bit after the data is visible, and a bucket only ends with nothing pending -- so at termination g is
@@ -159,12 +160,18 @@ __device__ __forceinline__ int kdi_of(int k) { return (k == 0 || k == 3 || k == 
 __device__ __forceinline__ int kdj_of(int k) { return k < 3 ? -1 : (k > 4 ? 1 : 0); }
 
 // Device view of one pipeline stage.  Global page index of query q's local page p >= 1 is q*cap + p; page 0 is
-// the shared "unreached" page.  Invariant between launches: every page word, aux word and tmap entry is 0, EXCEPT
-// what belongs to the local pages 1..nalloc[q] of each query; the next launch on the stage resets exactly those
-// (the workgroup that takes the slot next does, before it searches) instead of rewriting 64 MiB per query.
+// the slot's "unreached" page.
+// INVARIANT: a page's contents (its 1024 field words and words 0..31 of its aux block; words 32..63 are never read) are defined
+// only while a tile-map entry points at it; page 0 of a slot and its aux block are all zero and are never written.  Local pages
+// >= 1 without an entry hold whatever earlier searches of the slot left there -- or what the allocation held -- and nothing may
+// read them: every reader goes through tmap (TsaCtx::page_of in a tile job, tsa_backtrace_wave) or through the owner list of the
+// last search (tsa_settled_kernel: pages 1..nalloc[q] are the ones that search entered).  The job that hands a page out writes
+// it whole and enters it in tmap after those stores have been performed (tsa_job, results phase).
+// Between launches: every tmap entry is 0 EXCEPT those of the tiles owner[1..nalloc[q]] of each query; the workgroup that takes
+// the slot next resets exactly those before it searches -- 4 bytes per page the last search used, not the pages.
 struct TsaStage {
   unsigned* pages;      // [max_queries][cap + 1][1024]: local page 0 of a slot stays "unreached" (what a tile without a page reads)
-  unsigned* paux;       // [max_queries][cap + 1][64]
+  unsigned* paux;       // [max_queries][cap + 1][64]: a page's edge-column copies, [0] is page 0's and stays zero
   unsigned* tmap;       // [max_queries][ntile] tile -> local page, 0 = none
   unsigned* owner;      // [max_queries][cap + 1] local page -> tile
   int* nalloc;          // [max_queries] local pages handed out by the last search
@@ -255,10 +262,13 @@ __global__ void __launch_bounds__(256) tsa_prepare_kernel(TsaStage S, const rna_
     S.perm[rank] = i;
   }
 }
-// fresh allocation: every page "unreached"
-__global__ void tsa_fill_pages_kernel(uint4* __restrict__ p, size_t n4) {
-  const size_t step = (size_t)gridDim.x * blockDim.x;
-  for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < n4; w += step) p[w] = make_uint4(0u, 0u, 0u, 0u);
+// fresh allocation: page 0 of every slot and its aux block "unreached" -- all that has to be defined before a search (TsaStage).
+// One workgroup of 256 per slot: a uint4 of the page per thread, the aux block by the first sixteen.
+__global__ void __launch_bounds__(256) tsa_zero_page0_kernel(unsigned* __restrict__ pages, unsigned* __restrict__ paux, int cap) {
+  static_assert(TILE_WORDS / 4 == 256 && AUX_WORDS / 4 <= 256, "one uint4 of page 0 per thread");
+  const size_t page0 = (size_t)blockIdx.x * ((size_t)cap + 1);
+  reinterpret_cast<uint4*>(pages + (page0 << 10))[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+  if (threadIdx.x < AUX_WORDS / 4) reinterpret_cast<uint4*>(paux + page0 * AUX_WORDS)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
 }
 
 #ifdef RNA_TSA_STATS
@@ -1063,16 +1073,24 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
   // ---- 6. results: rows that changed, the edge-column copies, the goal ----
   asm volatile("" : "+v"(lane));
   if (rowchg) {
+    // `fresh`: this job gives the tile its page.  The page holds whatever the slot's earlier searches left in it (TsaStage), so
+    // this job writes it WHOLE -- all sixteen rows (the unchanged ones are the zeros it loaded from page 0) and both edge columns --
+    // and only then enters it in the tile map: a neighbour's job that finds the entry finds the page defined.
+    // (known here for the first time, a 32-bit scalar that lives until the entry is written below: nothing across the sweeps)
+    unsigned fresh = 0u;
     if (TSA_UNLIKELY(pg == 0u)) {   // first change of this tile: it gets a page (this job is the tile's only writer)
       int p = 0;
       if (lane == 0) {
         p = atomicAdd(C.nalloc, 1) + 1;
         if (p > C.cap) { p = 0; sch.pool_exhausted(); }
-        else { C.owner[p] = (unsigned)t; __hip_atomic_store(&C.tmap[t], (unsigned)p, __ATOMIC_RELAXED, TSA_SCOPE); }
+        else C.owner[p] = (unsigned)t;
       }
       pg = (unsigned)__builtin_amdgcn_readfirstlane(p);
       if (pg == 0u) return;   // (the search is being abandoned: status 5)
+      fresh = 1u;
     }
+    unsigned rowchg_store = fresh ? 0xffffu : rowchg;   // the rows to store; everything else below keeps reading `rowchg`
+    asm volatile("" : "+s"(rowchg_store));
     unsigned* own = C.pages + (pg << 10);
     unsigned* ax = C.paux + pg * AUX_WORDS + (lane ? 16 : 0);
     const bool edge_lane = __builtin_amdgcn_inverse_ballot_w64(0x8000000000000001ull);   // lanes 0 and 63 (as `lane == 0 || lane == 63` the compiler nests two exec-masked blocks)
@@ -1083,7 +1101,7 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
     // (the lane offset as an unsigned value of known range: the stores then take the page pointer as scalar base and
     // need no 64-bit vector address each)
     const unsigned ulane = (unsigned)lane & 63u;
-#define TSA_STORE(b) if ((rowchg >> (b)) & 1u) own[(b) * TI + ulane] = (unsigned)TSA_G(b);
+#define TSA_STORE(b) if ((rowchg_store >> (b)) & 1u) own[(b) * TI + ulane] = (unsigned)TSA_G(b);
     TSA_R16(TSA_STORE)
 #undef TSA_STORE
     if (TSA_UNLIKELY(ovf_possible)) {
@@ -1102,6 +1120,14 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
       a4[1] = make_uint4((unsigned)g4, (unsigned)g5, (unsigned)g6, (unsigned)g7);
       a4[2] = make_uint4((unsigned)g8, (unsigned)g9, (unsigned)g10, (unsigned)g11);
       a4[3] = make_uint4((unsigned)g12, (unsigned)g13, (unsigned)g14, (unsigned)g15);
+    }
+    if (TSA_UNLIKELY(fresh)) {
+      // the tile map points at the page once the page is in L2: a job of a neighbouring tile that runs meanwhile looks the entry up
+      // and reads this tile's edge row / column copy right away, and what is in the page until this job's stores arrive is an
+      // earlier search's field (a neighbour that still finds no entry reads page 0; it is woken below if this job has anything for
+      // it).  The entry itself is in L2 before a wake-up is queued and before the tile is released: both wait for it.
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane == 0) __hip_atomic_store(&C.tmap[t], pg, __ATOMIC_RELAXED, TSA_SCOPE);
     }
     if (ovfm && lane == 0) sch.overflow();   // path costs beyond 2^30 - 5656: the search is abandoned (status 4)
     if (TSA_UNLIKELY(t == C.tg)) {
@@ -1408,8 +1434,8 @@ __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const Tsa
   if (lane == 0) A.results[q] = rna_astar_result{0, len, r.cost, r.expanded, r.rounds, r.buckets};
 }
 
-// One workgroup of 8 wavefronts per query, four of them per CU.  The workgroup first resets the pages the slot's previous
-// search used, then searches; its first wavefront traces the path at the end (tsa_backtrace_wave).
+// One workgroup of 8 wavefronts per query, four of them per CU.  The workgroup first resets the tile-map entries the slot's
+// previous search made, then searches; its first wavefront traces the path at the end (tsa_backtrace_wave).
 // WAVES = wavefronts per workgroup (= per query): 8 when batches are pipelined (four queries share a CU, the throughput
 // configuration), 16 for a single batch on the engine's own stream and for batches of <= 32 queries (latency is what
 // counts there).
@@ -1499,18 +1525,16 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
       return;
     }
   }
-  // This query's pages as the last search in this slot left them: back to "unreached" (the slot is this workgroup's
-  // alone; its local pages 1..used are one contiguous run of the stage's page array).  Doing it here instead of in a
-  // kernel of its own takes ~1 ms off every turn of the stage, which can only take its next batch when this one's
-  // longest search has ended.
+  // This query's tile map as the last search in this slot left it: every entry that search made (its owner list names them) back
+  // to "no page" (the slot is this workgroup's alone).  The pages themselves stay as they are -- nothing reads a page the tile map
+  // does not point at, and the job that enters a page writes it whole first (TsaStage, tsa_job's results phase); zeroing them here
+  // was 4 352 bytes per page, 2.9 MB per search of the bench.  The entries are in L2 before the first job looks one up (the wait,
+  // then the barriers below).  Doing it here instead of in a kernel of its own takes ~1 ms off every turn of the stage, which can
+  // only take its next batch when this one's longest search has ended.
   {
     const int used_raw = S.nalloc[sl];
     const int used = used_raw < C.cap ? used_raw : C.cap;
     if (used > 0) {
-      uint4* pg4 = reinterpret_cast<uint4*>(C.pages + (1 << 10));
-      for (size_t w = tid; w < (size_t)used * (TILE_WORDS / 4); w += TSA_THREADS) pg4[w] = make_uint4(0u, 0u, 0u, 0u);
-      uint4* ax4 = reinterpret_cast<uint4*>(C.paux + AUX_WORDS);
-      for (size_t w = tid; w < (size_t)used * (AUX_WORDS / 4); w += TSA_THREADS) ax4[w] = make_uint4(0u, 0u, 0u, 0u);
       for (int p = 1 + tid; p <= used; p += TSA_THREADS) C.tmap[C.owner[p]] = 0u;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -1836,18 +1860,17 @@ static TsaStage tsa_retry_view(const rna_engine* e, int slot, const TsaStage& ma
   S.owner = reinterpret_cast<unsigned*>(base);
   return S;
 }
-int tsa_retry_prepare(rna_engine* e, int slot) {   // fresh retry pages: "unreached"
-  hipLaunchKernelGGL(tsa_fill_pages_kernel, dim3(2048), dim3(256), 0, e->stream, reinterpret_cast<uint4*>(e->astar.g_retry[slot]),
-                     tsa_retry_pool_bytes(e) / sizeof(uint4));
+int tsa_retry_prepare(rna_engine* e, int slot) {   // fresh retry slots: page 0 of each "unreached", the other pages as allocated
+  const TsaStage S = tsa_retry_view(e, slot, tsa_stage_view(e, slot));
+  hipLaunchKernelGGL(tsa_zero_page0_kernel, dim3(TSA_RETRY), dim3(256), 0, e->stream, S.pages, S.paux, S.cap);
   RNA_HIP(e, hipGetLastError());
   return RNA_OK;
 }
-// fresh stage: pages "unreached" (everything else was zeroed by the caller's hipMemsetAsync)
+// fresh stage: page 0 of every slot "unreached" (the tile maps and everything else were zeroed by the caller's hipMemsetAsync;
+// the other pages stay as allocated: no tile-map entry points at them) -- 4 352 bytes per slot instead of the whole pool
 int tsa_stage_prepare(rna_engine* e, int slot) {
   const TsaStage S = tsa_stage_view(e, slot);
-  const size_t pages = (size_t)e->astar.max_queries * ((size_t)S.cap + 1);
-  hipLaunchKernelGGL(tsa_fill_pages_kernel, dim3(8192), dim3(256), 0, e->stream, reinterpret_cast<uint4*>(S.pages),
-                     pages * (TILE_WORDS + AUX_WORDS) / 4);
+  hipLaunchKernelGGL(tsa_zero_page0_kernel, dim3(e->astar.max_queries), dim3(256), 0, e->stream, S.pages, S.paux, S.cap);
   RNA_HIP(e, hipGetLastError());
   return RNA_OK;
 }
@@ -1913,7 +1936,7 @@ int tsa_launch(rna_engine* e, int slot, hipStream_t init_stream, hipStream_t sea
     a.snap_pending[slot] = true;
   }
   {
-    // ticket and launch order (the pages of a slot are reset by the workgroup that takes the slot)
+    // ticket and launch order (the tile map of a slot is reset by the workgroup that takes the slot)
     KernelTimer kt(e, RNA_K_ASTAR_RESET, prep_stream);
     const int ranked = n <= 2048 ? 1 : 0;
     hipLaunchKernelGGL(tsa_prepare_kernel, dim3(1), dim3(256), ranked ? (size_t)n * sizeof(int) : 0, prep_stream, S, q_dev, n, rows, cols, ranked,

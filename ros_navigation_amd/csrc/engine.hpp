@@ -332,7 +332,7 @@ bool tsa_supported(const rna_engine* e);
 int tsa_tiles(const rna_engine* e);                                   // 32 x 32 tiles of the map
 size_t tsa_pool_bytes(int max_queries, int cap);                      // pages + pending bitmaps of one pipeline stage
 size_t tsa_aux_bytes(const rna_engine* e, int max_queries, int cap);  // per stage, must start zeroed
-int tsa_stage_prepare(rna_engine* e, int slot);                       // fresh stage: every page "unreached"
+int tsa_stage_prepare(rna_engine* e, int slot);                       // fresh stage: page 0 of every slot "unreached"
 constexpr int TSA_RETRY = 8;                                          // full-size retry slots per stage
 size_t tsa_retry_pool_bytes(const rna_engine* e);
 size_t tsa_retry_aux_bytes(const rna_engine* e);

@@ -1,0 +1,318 @@
+"""GPU parity tests of the grid-A* search pages across searches.  A query slot's pages are NOT cleaned between searches: the
+workgroup that takes a slot resets the tile map only, and the job that gives a tile its page writes the page whole before the tile
+map points at it (astar_tile.hip, TsaStage).  A page therefore holds an earlier search's field until it is handed out again, and
+any read that does not go through the tile map -- or a page that is entered before it is written -- shows up as a wrong cost, path
+or settled count in the search that follows in the slot.  Every batch here is compared with the CPU oracle: status, cost, length,
+every path cell and the settled count (rna_astar_settled_counts reads the whole field of the slot's last search).
+
+Shapes: 256 x 192 cells = 4 x 12 search tiles of 64 x 16, and 200 x 150 = 4 x 10 with partial tiles on both far edges; 16 queries
+per batch (the sixteen-wavefront kernel), once 40 (the pipelined eight-wavefront kernel); pipeline depth 1 and 2.  The synchronous
+entry point takes the stage that has been free the longest, so a batch that is run `depth` times in a row has visited every stage:
+the batch after it meets its leftovers in every slot of every stage.
+
+Whether the inputs can tell a leak is asserted on the CPU, from the oracle's g arrays, before the GPU runs (the seeds below were
+chosen there); no build with the reset broken was run on a GPU to prove it -- a stale field can send the path walk round in circles."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+from ros_navigation_amd import synth
+
+import _oracle as O
+from _gpu import R, make_engine_and_geom, to_buffer, to_map  # noqa: F401  (R: the fixture)
+from test_gpu_parity import check_astar
+
+pytestmark = pytest.mark.gpu
+
+INF = 0x7fffffff
+NQ = 16
+MAPS = {"whole_tiles": (256, 192, 31), "partial_tiles": (200, 150, 32)}   # rows, cols, seed of the rectangles
+CORNERS = ((0, 0), (1, 1), (1, 0), (0, 1))
+
+
+@functools.lru_cache(maxsize=None)
+def the_map(name):
+    rows, cols, seed = MAPS[name]
+    master = synth.obstacles_rect(rows, cols, density=0.2, seed=seed, side=(3, 20))
+    master.setflags(write=False)
+    free = np.flatnonzero(synth.free_component(master, rows, cols))
+    return rows, cols, master, free
+
+
+def corner_cells(free, rows, cols, corner, frac=0.2):
+    """cells of the free component inside the box of `frac` of either side at a corner of the map"""
+    i, j = free % rows, free // rows
+    wi, wj = int(rows * frac), int(cols * frac)
+    mi = (i < wi) if corner[0] == 0 else (i >= rows - wi)
+    mj = (j < wj) if corner[1] == 0 else (j >= cols - wj)
+    return free[mi & mj]
+
+
+def corner_queries(name, n, seed, reverse=False):
+    """slot k: from the corner CORNERS[k % 4] to the corner opposite -- `reverse`: the same cells the other way, so that the two
+    searches of a slot cross the same part of the map with g counted from opposite ends"""
+    rows, cols, _, free = the_map(name)
+    rng = np.random.default_rng(seed)
+    q = np.zeros(n, synth.ASTAR_QUERY_DTYPE)
+    for k in range(n):
+        c = CORNERS[k % 4]
+        a = rng.choice(corner_cells(free, rows, cols, c))
+        b = rng.choice(corner_cells(free, rows, cols, (1 - c[0], 1 - c[1])))
+        q["start"][k], q["goal"][k] = (b, a) if reverse else (a, b)
+    return q
+
+
+def oracle_fields(name, q, master=None):
+    """[(result, path, g array)] of the oracle, one per query"""
+    rows, cols, m0, _ = the_map(name)
+    _, nbr = O.astar_masks(m0 if master is None else master, rows, cols)
+    return [O.astar_query(nbr, rows, cols, q["start"][k], q["goal"][k]) for k in range(len(q))]
+
+
+def octile(cells, goal, rows):
+    di, dj = np.abs(cells % rows - goal % rows), np.abs(cells // rows - goal // rows)
+    return 1000 * np.maximum(di, dj) + 414 * np.minimum(di, dj)
+
+
+def settled_set(rows, res, g, goal):
+    """the cells the contract settles: g + h <= f* (what the search's pages must hold exactly)"""
+    cells = np.arange(g.size)
+    return (g != INF) & (g.astype(np.int64) + octile(cells, int(goal), rows) <= res.cost)
+
+
+def tiles_of(rows, cells_mask):
+    c = np.flatnonzero(cells_mask)
+    return set((((c // rows) >> 4) * ((rows + 63) // 64) + ((c % rows) >> 6)).tolist())
+
+
+def engine_for(R, name, depth, max_queries=NQ, bucket_width=0):
+    rows, cols, master, _ = the_map(name)
+    e, g = make_engine_and_geom(R, rows, cols, master.copy())
+    e.astar_pipeline_depth(depth)
+    e.astar_configure(max_queries=max_queries, bucket_width=bucket_width)
+    return e, g
+
+
+def every_stage(R, e, master, q, depth, **kw):
+    """the batch once on every pipeline stage, each run checked against the oracle"""
+    for _ in range(depth):
+        res, _ = check_astar(R, e, master, q, e.ncell, **kw)
+    return res
+
+
+# ---- case 1: other queries on pages that hold old values ----
+SEED_A = {"whole_tiles": 2, "partial_tiles": 3}     # of seeds 1..11 the ones for which every premise below holds, 40 slots included
+
+
+def leak_premise(name, n):
+    """batches A and B, after the CPU has confirmed that a leak from A into B (or from B back into A) would change B's field: in every slot
+    both searches found a path, they settle at least a tile's worth of common cells, and at least a quarter of those carry
+    different g in the two searches"""
+    rows, cols, _, _ = the_map(name)
+    qa, qb = corner_queries(name, n, SEED_A[name]), corner_queries(name, n, SEED_A[name], reverse=True)
+    fa, fb = oracle_fields(name, qa), oracle_fields(name, qb)
+    for k in range(n):
+        (ra, _, ga), (rb, _, gb) = fa[k], fb[k]
+        assert ra.status == 0 and rb.status == 0, (name, k)
+        both = settled_set(rows, ra, ga, qa["goal"][k]) & settled_set(rows, rb, gb, qb["goal"][k])
+        differ = int((ga[both] != gb[both]).sum())
+        assert both.sum() >= 1024 and 4 * differ >= both.sum(), (name, k, int(both.sum()), differ)
+    return qa, qb
+
+
+@pytest.mark.parametrize("depth,n,bucket_width", [(1, NQ, 2828), (2, NQ, 2828), (2, NQ, 128000), (2, 40, 128000)])
+@pytest.mark.parametrize("name", sorted(MAPS))
+def test_other_queries_on_pages_that_hold_old_values(R, name, depth, n, bucket_width):
+    qa, qb = leak_premise(name, n)
+    _, _, master, _ = the_map(name)
+    e, _ = engine_for(R, name, depth, max_queries=n, bucket_width=bucket_width)
+    for q in (qa, qb, qa):
+        every_stage(R, e, master, q, depth)
+    e.close()
+
+
+# ---- case 2: subset, then superset ----
+def subset_premise(name):
+    """long searches L and, slot by slot, a short search S from the same start to the 11th cell of L's path, whose tiles (every
+    cell the oracle reached) are a strict subset of L's"""
+    rows, cols, _, _ = the_map(name)
+    ql = corner_queries(name, NQ, SEED_A[name])
+    fl = oracle_fields(name, ql)
+    qs = ql.copy()
+    for k in range(NQ):
+        assert fl[k][0].status == 0 and fl[k][0].path_len > 40, (name, k)
+        qs["goal"][k] = fl[k][1][10]
+    fs = oracle_fields(name, qs)
+    for k in range(NQ):
+        tl, ts = tiles_of(rows, fl[k][2] != INF), tiles_of(rows, fs[k][2] != INF)
+        assert fs[k][0].status == 0 and ts < tl, (name, k, len(ts), len(tl))
+    return ql, qs
+
+
+@pytest.mark.parametrize("depth", [1, 2])
+@pytest.mark.parametrize("name", sorted(MAPS))
+def test_subset_then_superset(R, name, depth):
+    """a tile that search 1 and search 3 of a slot map and search 2 does not: its page number of search 1 must not survive search 2"""
+    ql, qs = subset_premise(name)
+    _, _, master, _ = the_map(name)
+    e, _ = engine_for(R, name, depth, bucket_width=2828)
+    touched = []
+    for q in (ql, qs, ql):
+        every_stage(R, e, master, q, depth)
+        touched.append(e.astar_job_counters(reset=True)["tiles_touched"])
+    assert touched[1] < touched[0] and touched[1] < touched[2], touched     # the kernel's own count: the short searches took fewer pages
+    e.close()
+
+
+# ---- case 3: the map changed in between ----
+def changed_map(name, qa, fa):
+    """the map with a dozen new rectangles on cells that A's searches settled (never on a start or a goal)"""
+    rows, cols, master, _ = the_map(name)
+    rng = np.random.default_rng(77)
+    reached = np.zeros(rows * cols, bool)
+    for k in range(len(qa)):
+        reached |= settled_set(rows, fa[k][0], fa[k][2], qa["goal"][k])
+    m = master.copy().reshape(cols, rows)
+    keep = np.zeros((cols, rows), bool)
+    for c in np.concatenate([qa["start"], qa["goal"]]):
+        keep[max(0, c // rows - 1):c // rows + 2, max(0, c % rows - 1):c % rows + 2] = True
+    cand = np.flatnonzero(reached)
+    placed = 0
+    while placed < 12:
+        c = int(rng.choice(cand))
+        w, h = rng.integers(3, 11, 2)
+        i0, j0 = c % rows, c // rows
+        if keep[j0:j0 + h, i0:i0 + w].any():
+            continue
+        m[j0:j0 + h, i0:i0 + w] = 180.0
+        placed += 1
+    return m.reshape(-1).copy()
+
+
+@pytest.mark.parametrize("depth", [1, 2])
+@pytest.mark.parametrize("name", sorted(MAPS))
+def test_map_changed_between_two_searches_of_a_slot(R, name, depth):
+    qa = corner_queries(name, NQ, SEED_A[name])
+    fa = oracle_fields(name, qa)
+    master2 = changed_map(name, qa, fa)
+    fb = oracle_fields(name, qa, master2)
+    changed = sum((a[0].status, a[0].cost, a[0].settled) != (b[0].status, b[0].cost, b[0].settled) for a, b in zip(fa, fb))
+    assert changed >= NQ // 2, changed      # the new rectangles matter to the searches
+    _, _, master, _ = the_map(name)
+    e, _ = engine_for(R, name, depth)
+    every_stage(R, e, master, qa, depth)
+    e.upload(R.capi.LAYER_LASER, master2)
+    e.compose_master(1)
+    every_stage(R, e, master2, qa, depth)
+    e.close()
+
+
+# ---- case 4: early returns in a used slot ----
+def check_on_map(e, g, ref, q):
+    """a batch against the oracle's search in map space (og_astar_query_on_map: also right after GridMap::move)"""
+    res, paths = e.astar(q, e.ncell)
+    settled = e.astar_settled(len(q))
+    for k in range(len(q)):
+        ores, opath = O.astar_query_on_map(g, ref, q["start"][k], q["goal"][k])
+        assert res["status"][k] == ores.status, (k, q[k], res[k])
+        if ores.status == 0:
+            assert res["cost"][k] == ores.cost and res["path_len"][k] == ores.path_len, (k, q[k], res[k])
+            assert np.array_equal(paths[k, :ores.path_len], opath), (k, q[k])
+            assert settled[k] == ores.settled, (k, q[k], settled[k], ores.settled)
+    return res
+
+
+@pytest.mark.parametrize("moved", [False, True])
+@pytest.mark.parametrize("depth", [1, 2])
+@pytest.mark.parametrize("name", sorted(MAPS))
+def test_early_returns_in_a_used_slot(R, name, depth, moved):
+    """A walled-in start, an invalid index and start == goal in a slot that held a long search: the first two are answered before
+    the tile map is reset and leave the slot's page count to the search after them (a normal query, checked), start == goal is a
+    search of one cell.  Every slot sees all three kinds, a normal query after each."""
+    rows, cols, master, _ = the_map(name)
+    e, g = engine_for(R, name, depth)
+    ref = master.copy()
+    if moved:
+        for layer in range(3):
+            e.upload(layer, ref)
+        ptrs = (C.POINTER(C.c_float) * 1)(O.fptr(ref))
+        regs, mv = (O.Region * 4)(), C.c_int(0)
+        target = (0.31 * rows * 0.05, -0.27 * cols * 0.05)
+        O.lib().og_move(C.byref(g), ptrs, 1, O.d2(*target), regs, C.byref(mv))
+        assert e.move(*target) and tuple(e.geometry().start_index) == tuple(g.start) and 0 not in tuple(g.start)
+    s0, s1 = g.start[0], g.start[1]
+    # in map space: a free cell ringed by blocked ones, away from the map's edges
+    m = to_map(ref, rows, cols, s0, s1).copy()
+    wi, wj = rows // 2 + 3, cols // 2 + 2
+    m[wj - 1:wj + 2, wi - 1:wi + 2] = 180.0
+    m[wj, wi] = 0.0
+    ref = to_buffer(m.reshape(-1), rows, cols, s0, s1)
+    e.upload(R.capi.LAYER_MASTER, ref)
+
+    def buf(lin):     # map-space linear index -> buffer linear index
+        lin = np.asarray(lin)
+        return ((lin % rows + s0) % rows + ((lin // rows + s1) % cols) * rows).astype(np.int32)
+
+    walled = int(buf(wj * rows + wi))
+    mflat = m.reshape(-1)
+    free = np.flatnonzero(synth.free_component(mflat, rows, cols))
+    rng = np.random.default_rng(11)
+
+    def long_batch():
+        q = np.zeros(NQ, R.capi.ASTAR_QUERY_DTYPE)
+        for k in range(NQ):   # (after a move the old border wall cuts the new strips off: no corners, the farthest of 64 cells of the component)
+            a = int(rng.choice(free))
+            cand = rng.choice(free, 64)
+            b = int(cand[np.argmax(np.maximum(np.abs(cand % rows - a % rows), np.abs(cand // rows - a // rows)))])
+            q["start"][k], q["goal"][k] = buf(a), buf(b)
+        return q
+
+    def normal_batch():
+        q = np.zeros(NQ, R.capi.ASTAR_QUERY_DTYPE)
+        q["start"], q["goal"] = buf(rng.choice(free, NQ)), buf(rng.choice(free, NQ))
+        return q
+
+    def early_batch(turn):
+        q = normal_batch()
+        kinds = (np.arange(NQ) + turn) % 3
+        q["start"][kinds == 0] = walled
+        q["start"][(kinds == 1) & (np.arange(NQ) % 2 == 0)] = -1
+        q["goal"][(kinds == 1) & (np.arange(NQ) % 2 == 1)] = rows * cols
+        q["goal"][kinds == 2] = q["start"][kinds == 2]
+        return q, kinds
+
+    for _ in range(depth):
+        res = check_on_map(e, g, ref, long_batch())
+        assert (res["status"] == 0).sum() >= NQ // 2      # the slots hold long searches
+    for turn in range(3):
+        q, kinds = early_batch(turn)
+        for _ in range(depth):
+            res = check_on_map(e, g, ref, q)
+            assert np.all(res["status"][kinds == 0] == 1) and np.all(res["status"][kinds == 1] == 2), res["status"]
+            assert np.all(res["buckets"][kinds != 2] == 0)           # answered before the search started
+            assert np.all(res["status"][kinds == 2] == 0) and np.all(res["path_len"][kinds == 2] == 1)
+        q = normal_batch()
+        for _ in range(depth):
+            check_on_map(e, g, ref, q)
+    e.close()
+
+
+# ---- case 5: the retry slots, reused with their pages as the last second pass left them ----
+@pytest.mark.parametrize("depth", [1, 2])
+@pytest.mark.parametrize("name", sorted(MAPS))
+def test_retry_slots_are_reused_as_they_were_left(R, name, depth):
+    """three pages per query (rna_astar_set_page_cap, as tests/test_gpu_parity.py makes searches outgrow their share): the long searches
+    end their first pass with status 5 and run again in the stage's eight retry slots, batch after batch on one engine"""
+    rows, cols, master, _ = the_map(name)
+    qa, qb = corner_queries(name, 8, SEED_A[name]), corner_queries(name, 8, SEED_A[name], reverse=True)
+    for q in (qa, qb):
+        assert sum(f[0].settled > 3 * 1024 for f in oracle_fields(name, q)) >= 4      # (a tile holds 1024 cells)
+    e, g = engine_for(R, name, depth, max_queries=8, bucket_width=2828)
+    e.astar_page_cap(3)
+    for q in (qa, qb, qa):
+        for _ in range(depth):
+            check_on_map(e, g, master, q)
+            assert e.astar_effective_config()[1] == 3
+    e.close()
