@@ -45,7 +45,7 @@ struct HostTrace {
   void dump() {
     if (!on || n == 0) return;
     fprintf(stderr, "[host trace] %ld pipelined launches, us each: wait for a free stage %.1f (%.2f hipEventQuery calls) | ring entry's old batch %.1f | "
-            "tsa_launch (events, snapshot, launch order, search, flag copy) %.1f | done event + bookkeeping %.1f\n", n, us[0] / n, (double)queries / n,
+            "enqueue (events, snapshot, launch order, search, flag copy) %.1f | done event + bookkeeping %.1f\n", n, us[0] / n, (double)queries / n,
             us[1] / n, us[2] / n, us[3] / n);
     for (double& v : us) v = 0;
     n = 0; queries = 0;
@@ -54,12 +54,12 @@ struct HostTrace {
 HostTrace g_trace;
 // (RNA_HOST_TRACE) a stage's cycle in GPU time: event A when the stage's stream reaches the new batch (it is idle: at enqueue),
 // C when the search and what follows it on the stream have ended; host clock: enqueue and "noticed free".  (With a third event
-// where the search's last wait ends -- inside tsa_launch, a temporary hook -- round 6 measured 4.46 ms from enqueue until the
-// search may start, 22.40 ms of search, 27.89 ms until the host has noticed: profiles/r06_host_trace.txt.)
+// where the search's last wait ends -- in front of the search launch, a temporary hook -- round 6 measured 4.46 ms from enqueue
+// until the search may start, 22.40 ms of search, 27.89 ms until the host has noticed: profiles/r06_host_trace.txt.)
 struct StageTrace {
-  hipEvent_t a[32] = {}, c[32] = {};
-  std::chrono::steady_clock::time_point t_enq[32];
-  bool armed[32] = {};
+  hipEvent_t a[AstarDevice::MAX_DEPTH] = {}, c[AstarDevice::MAX_DEPTH] = {};
+  std::chrono::steady_clock::time_point t_enq[AstarDevice::MAX_DEPTH];
+  bool armed[AstarDevice::MAX_DEPTH] = {};
   double gpu_ms = 0, host_busy_ms = 0;
   long n = 0;
 };
@@ -70,91 +70,86 @@ void stage_trace_dump() {
   g_stage.gpu_ms = g_stage.host_busy_ms = 0; g_stage.n = 0;
 }
 
-// allocation of the configuration ensure_config settled on; everything is released again on failure
-static int alloc_stages_impl(rna_engine* e) {
+#define RNA_TRY(call) do { const int rc_try_ = (call); if (rc_try_ != RNA_OK) return rc_try_; } while (0)
+
+// one stage of the configuration ensure_config settled on (a released stage: every member is at its default)
+int alloc_stage(rna_engine* e, int d) {
   AstarDevice& a = e->astar;
-  int rc;
-  for (int d = 0; d < a.depth; ++d) {
-    {
-      char* pool = nullptr;
-      if ((rc = dev_alloc(e, &pool, tsa_pool_bytes(a.max_queries, a.page_cap))) != RNA_OK) { astar_release(e); return rc; }
-      a.g[d] = reinterpret_cast<int32_t*>(pool);
-      if ((rc = dev_alloc(e, &a.rev[d], (size_t)a.rev_cap * a.max_queries)) != RNA_OK) { astar_release(e); return rc; }
-      char* aux = nullptr;
-      const size_t aux_bytes = tsa_aux_bytes(e, a.max_queries, a.page_cap);
-      if ((rc = dev_alloc(e, &aux, aux_bytes)) != RNA_OK) { astar_release(e); return rc; }
-      a.tsa_aux[d] = aux;
-      RNA_HIP(e, hipMemsetAsync(aux, 0, aux_bytes, e->stream));
-      if ((rc = tsa_stage_prepare(e, d)) != RNA_OK) { astar_release(e); return rc; }
-      if (a.page_cap < tsa_tiles(e)) {   // a search may outgrow its share of pages: retry slots with a page per tile
-        char* rp = nullptr;
-        if ((rc = dev_alloc(e, &rp, tsa_retry_pool_bytes(e))) != RNA_OK) { astar_release(e); return rc; }
-        a.g_retry[d] = reinterpret_cast<int32_t*>(rp);
-        char* ra = nullptr;
-        if ((rc = dev_alloc(e, &ra, tsa_retry_aux_bytes(e))) != RNA_OK) { astar_release(e); return rc; }
-        a.tsa_aux_retry[d] = ra;
-        const hipError_t me = hipMemsetAsync(ra, 0, tsa_retry_aux_bytes(e), e->stream);
-        if (me != hipSuccess) { astar_release(e); RNA_HIP(e, me); }
-        if ((rc = tsa_retry_prepare(e, d)) != RNA_OK) { astar_release(e); return rc; }
-      }
-    }
-    if (a.depth > 1) {
-      {
-        // searches run at the lowest queue priority, the engine stream (map update, VFH+, field reset) at the highest:
-        // its short kernels gate the next search launch and must not queue behind 1000 waiting search workgroups
-        int prio_lo = 0, prio_hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        if (getenv("RNA_NO_STREAM_PRIORITY")) prio_lo = prio_hi = 0;
-        // The search streams may not use one CU in eight (ROCr deals the bits of a queue's CU mask round-robin to the
-        // XCDs, so the first n bits are n / 8 CUs of every XCD).  A search workgroup holds its CU slot for a whole query
-        // (milliseconds) and four of them fill a CU's registers, so a stream priority cannot make room for the engine
-        // stream's short kernels (map update, VFH+, field reset) that gate the next search launch: without the reserve
-        // they take 3 ms instead of 0.3 ms each and the step rate hangs on them (22 k instead of 33 k cycles/s when this
-        // was introduced; with the final kernel 16 / 24 / 32 / 40 / 48 reserved CUs: 74.6 / 78.8 / 80.5 / 78.8 / 76.7 k).
-        // RNA_SEARCH_CU_SKIP=n overrides the number of reserved CUs, 0 = no mask (stream priority only).
-        int skip = e->cu_count / 8;
-        if (const char* m = getenv("RNA_SEARCH_CU_SKIP")) skip = atoi(m);
-        if (skip > 0 && skip < e->cu_count) {
-          uint32_t mask[16] = {};
-          const int words = (e->cu_count + 31) / 32 < 16 ? (e->cu_count + 31) / 32 : 16;
-          for (int c = skip; c < e->cu_count && c < 512; ++c) mask[c >> 5] |= 1u << (c & 31);
-          RNA_HIP(e, hipExtStreamCreateWithCUMask(&a.side[d], (uint32_t)words, mask));
-        } else {
-          RNA_HIP(e, hipStreamCreateWithPriority(&a.side[d], hipStreamNonBlocking, prio_lo));
-        }
-      }
-      RNA_HIP(e, hipEventCreateWithFlags(&a.done[d], hipEventDisableTiming));
-      RNA_HIP(e, hipEventCreateWithFlags(&a.snap_done[d], hipEventDisableTiming));
-    }
-    a.snap_pending[d] = false;
-    a.busy[d] = false;
-    a.stage_seq[d] = 0;
+  AstarStage& s = a.stage[d];
+  RNA_TRY(dev_alloc(e, &s.pool, tsa_pool_bytes(a.max_queries, a.page_cap) / sizeof(unsigned)));
+  RNA_TRY(dev_alloc(e, &s.rev, (size_t)a.rev_cap * a.max_queries));
+  RNA_TRY(dev_alloc(e, &s.block, tsa_stage_bytes(e)));
+  RNA_HIP(e, hipMemsetAsync(s.block, 0, tsa_stage_bytes(e), e->stream));
+  RNA_TRY(tsa_stage_prepare(e, d));
+  if (a.page_cap < tsa_tiles(e)) {   // a search may outgrow its share of pages: retry slots with a page per tile
+    RNA_TRY(dev_alloc(e, &s.retry_pool, tsa_retry_pool_bytes(e) / sizeof(unsigned)));
+    RNA_TRY(dev_alloc(e, &s.retry_block, tsa_retry_bytes(e)));
+    RNA_HIP(e, hipMemsetAsync(s.retry_block, 0, tsa_retry_bytes(e), e->stream));
+    RNA_TRY(tsa_retry_prepare(e, d));
   }
+  if (a.depth == 1) return RNA_OK;
+  // searches run at the lowest queue priority, the engine stream (map update, VFH+, field reset) at the highest:
+  // its short kernels gate the next search launch and must not queue behind 1000 waiting search workgroups
+  int prio_lo = 0, prio_hi = 0;
+  (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+  if (getenv("RNA_NO_STREAM_PRIORITY")) prio_lo = prio_hi = 0;
+  // The search streams may not use one CU in eight (ROCr deals the bits of a queue's CU mask round-robin to the
+  // XCDs, so the first n bits are n / 8 CUs of every XCD).  A search workgroup holds its CU slot for a whole query
+  // (milliseconds) and four of them fill a CU's registers, so a stream priority cannot make room for the engine
+  // stream's short kernels (map update, VFH+, field reset) that gate the next search launch: without the reserve
+  // they take 3 ms instead of 0.3 ms each and the step rate hangs on them (22 k instead of 33 k cycles/s when this
+  // was introduced; with the final kernel 16 / 24 / 32 / 40 / 48 reserved CUs: 74.6 / 78.8 / 80.5 / 78.8 / 76.7 k).
+  // RNA_SEARCH_CU_SKIP=n overrides the number of reserved CUs, 0 = no mask (stream priority only).
+  int skip = e->cu_count / 8;
+  if (const char* m = getenv("RNA_SEARCH_CU_SKIP")) skip = atoi(m);
+  if (skip > 0 && skip < e->cu_count) {
+    uint32_t mask[16] = {};
+    const int words = (e->cu_count + 31) / 32 < 16 ? (e->cu_count + 31) / 32 : 16;
+    for (int c = skip; c < e->cu_count && c < 512; ++c) mask[c >> 5] |= 1u << (c & 31);
+    RNA_HIP(e, hipExtStreamCreateWithCUMask(&s.stream, (uint32_t)words, mask));
+  } else {
+    RNA_HIP(e, hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, prio_lo));
+  }
+  RNA_HIP(e, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+  RNA_HIP(e, hipEventCreateWithFlags(&s.snap_done, hipEventDisableTiming));
+  return RNA_OK;
+}
+
+void free_stage(AstarStage& s) {
+  dev_free(&s.pool); dev_free(&s.rev); dev_free(&s.block); dev_free(&s.retry_pool); dev_free(&s.retry_block);
+  if (s.stream) (void)hipStreamDestroy(s.stream);
+  if (s.done) (void)hipEventDestroy(s.done);
+  if (s.snap_done) (void)hipEventDestroy(s.snap_done);
+  s = AstarStage{};
+}
+
+// allocation of the whole configuration; errors are returned as they come, alloc_stages cleans up
+int alloc_stages_impl(rna_engine* e) {
+  AstarDevice& a = e->astar;
+  for (int d = 0; d < a.depth; ++d) RNA_TRY(alloc_stage(e, d));
   if (a.depth > 1) {
     RNA_HIP(e, hipEventCreateWithFlags(&a.ev_init, hipEventDisableTiming));
     RNA_HIP(e, hipEventCreateWithFlags(&a.ev_prep, hipEventDisableTiming));
     a.ring_n = 2 * a.depth;
-    a.ring_stride = tsa_ring_bytes(e, a.max_queries);
-    if ((rc = dev_alloc(e, &a.ring_mem, a.ring_stride * (size_t)a.ring_n)) != RNA_OK) return rc;
+    a.ring_stride = tsa_ring_bytes(e);
+    RNA_TRY(dev_alloc(e, &a.ring_mem, a.ring_stride * (size_t)a.ring_n));
     RNA_HIP(e, hipMemsetAsync(a.ring_mem, 0, a.ring_stride * (size_t)a.ring_n, e->stream));
-    for (int r = 0; r < a.ring_n; ++r) {
-      RNA_HIP(e, hipEventCreateWithFlags(&a.ring_free[r], hipEventDisableTiming));
-      a.ring_used[r] = false;
-    }
+    for (int r = 0; r < a.ring_n; ++r) RNA_HIP(e, hipEventCreateWithFlags(&a.ring[r].free, hipEventDisableTiming));
   }
-  if (a.g_retry[0]) {
+  if (a.stage[0].retry_pool) {
     RNA_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&a.retry_flag), AstarDevice::MAX_DEPTH * sizeof(int), hipHostMallocCoherent));
     for (int d = 0; d < AstarDevice::MAX_DEPTH; ++d) a.retry_flag[d] = 0;
+    for (int d = 0; d < a.depth; ++d) a.stage[d].retry_flag = a.retry_flag + d;
   }
   a.launches = 0;
-  if ((rc = dev_alloc(e, &a.queries_dev, (size_t)a.max_queries)) != RNA_OK) { astar_release(e); return rc; }
-  if ((rc = dev_alloc(e, &a.results_dev, (size_t)a.max_queries)) != RNA_OK) { astar_release(e); return rc; }
+  RNA_TRY(dev_alloc(e, &a.queries_dev, (size_t)a.max_queries));
+  RNA_TRY(dev_alloc(e, &a.results_dev, (size_t)a.max_queries));
   return RNA_OK;
 }
 
-// (whatever fails inside -- an allocation, a memset, a stream or an event -- nothing half-built is left behind: the next
-// call starts from nothing again instead of finding a[0] allocated and taking the configuration for complete)
-static int alloc_stages(rna_engine* e) {
+// (whatever fails inside -- an allocation, a memset, a stream or an event -- nothing half-built is left behind: the next call starts
+// from nothing again instead of finding stage 0 allocated and taking the configuration for complete; the first error's text is kept)
+int alloc_stages(rna_engine* e) {
   const int rc = alloc_stages_impl(e);
   if (rc != RNA_OK) {
     const std::string why = e->err;
@@ -166,11 +161,10 @@ static int alloc_stages(rna_engine* e) {
 
 int ensure_config(rna_engine* e) {
   AstarDevice& a = e->astar;
-  if (a.g[0]) return RNA_OK;
+  if (a.live()) return RNA_OK;
   if (a.max_queries <= 0) a.max_queries = 256;
   if (!tsa_supported(e)) return fail(e, RNA_EINVAL, "grid A*: more than 65 536 tiles of 64 x 16 cells (8192 x 8192 cells): tile numbers are 16 bits");
-  if (a.depth < 1) a.depth = 1;
-  if (a.depth > AstarDevice::MAX_DEPTH) a.depth = AstarDevice::MAX_DEPTH;
+  a.depth = std::clamp(a.depth, 1, (int)AstarDevice::MAX_DEPTH);
   // fit into free HBM (25 % headroom): fewer pages per query (half a map's worth), fewer pipeline stages, fewer pages
   // still -- a search that needs more than its share is searched again on a full-size retry slot (astar_tile.hip: eight
   // at a time, as many passes as it takes; status 5 is transient and never final) --, then fewer concurrent queries
@@ -181,9 +175,8 @@ int ensure_config(rna_engine* e) {
   if (a.page_cap_request > 0 && a.page_cap_request < ntile) a.page_cap = a.page_cap_request;
   if (const char* c = getenv("RNA_ASTAR_PAGE_CAP")) { const int v = atoi(c); if (v > 0 && v < ntile) a.page_cap = v; }
   auto stage_bytes = [&]() -> double {
-    return (double)tsa_pool_bytes(a.max_queries, a.page_cap) + (double)tsa_aux_bytes(e, a.max_queries, a.page_cap) +
-           (double)a.rev_cap * 4.0 * a.max_queries +
-           (a.page_cap < ntile ? (double)tsa_retry_pool_bytes(e) + (double)tsa_retry_aux_bytes(e) : 0.0);
+    return (double)tsa_pool_bytes(a.max_queries, a.page_cap) + (double)tsa_stage_bytes(e) + (double)a.rev_cap * 4.0 * a.max_queries +
+           (a.page_cap < ntile ? (double)tsa_retry_pool_bytes(e) + (double)tsa_retry_bytes(e) : 0.0);
   };
   // (tile kernel) half a map's worth of pages per query first -- searches touch a few per cent of the map, and twelve
   // stages of 17.8 GB each at 4096^2 x 256 queries sit right at the budget --, then fewer stages, then fewer pages
@@ -204,133 +197,165 @@ int ensure_config(rna_engine* e) {
   }
 }
 
-// The stage's search has finished (its `done` event is complete): if searches of that batch ran out of pages, their
-// second pass goes out now and the stage stays busy (returns true).
-static bool stage_settled(rna_engine* e, int d, int* rc) {
-  AstarDevice& a = e->astar;
-  *rc = RNA_OK;
-  if (!a.retry_armed[d]) return true;
-  a.retry_armed[d] = false;
-  if (!a.retry_flag || a.retry_flag[d] == 0) return true;
-  const int count = a.retry_flag[d];
-  a.retry_flag[d] = 0;
-  a.last_retried[d] = count;
-  hipStream_t st = a.depth > 1 ? a.side[d] : e->stream;
-  *rc = tsa_retry_launch(e, d, st, count);
-  if (*rc != RNA_OK) return true;
-  if (a.depth > 1 && hipEventRecord(a.done[d], st) != hipSuccess) { *rc = fail(e, RNA_EHIP, "hipEventRecord"); return true; }
-  return false;
+hipStream_t stage_stream(rna_engine* e, int d) { return e->astar.depth > 1 ? e->astar.stage[d].stream : e->stream; }
+// the stage's last batch may have something left to do: the host has not seen `done` complete; one stream: a second pass may be due
+bool stage_pending(const AstarDevice& a, int d) { return a.depth > 1 ? a.stage[d].busy : a.stage[d].retry_armed; }
+
+// The stage's search has finished (the host has seen its `done` event, or the engine stream, complete): if searches of that
+// batch ran out of pages, their second pass goes out now (*sent) and `done` is recorded behind it again.
+int stage_settled(rna_engine* e, int d, bool* sent) {
+  AstarStage& s = e->astar.stage[d];
+  *sent = false;
+  if (!s.retry_armed) return RNA_OK;
+  s.retry_armed = false;
+  if (!s.retry_flag || *s.retry_flag == 0) return RNA_OK;
+  const int count = *s.retry_flag;
+  *s.retry_flag = 0;
+  s.last_retried = count;
+  RNA_TRY(tsa_retry_launch(e, d, stage_stream(e, d), count));
+  if (e->astar.depth > 1) RNA_HIP(e, hipEventRecord(s.done, s.stream));
+  *sent = true;
+  return RNA_OK;
 }
 
-// One batch (<= max_queries): mask snapshot + launch order on the side stream (it reads the neighbour masks, which the
-// next map update may overwrite), then the search on a pipeline stage's own stream.
-int launch_chunk(rna_engine* e, const rna_astar_query* q_dev, int n, int32_t* paths_dev, int max_len,
-                 rna_astar_result* res_dev, int* slot_out) {
+// The host waits for the stage's last batch, second passes included (as many as it takes; status 5 is never final).
+int stage_wait(rna_engine* e, int d) {
+  AstarStage& s = e->astar.stage[d];
+  for (bool sent = true; sent;) {
+    if (e->astar.depth > 1) RNA_HIP(e, hipEventSynchronize(s.done));
+    else RNA_HIP(e, hipStreamSynchronize(e->stream));
+    RNA_TRY(stage_settled(e, d, &sent));
+  }
+  s.busy = false;
+  return RNA_OK;
+}
+
+// Which stage the next batch goes to (pipelined).  On return the host has seen the stage free (except under RNA_ASTAR_NOWAIT),
+// and the batch that last read the ring entry this launch will write is over and settled.
+int pick_stage(rna_engine* e, int* slot_out) {
   AstarDevice& a = e->astar;
   // Which stage: one that IS free, the one that has been free the longest -- not simply the next in turn.  A batch lasts
   // as long as its longest search; taking the stages strictly in turn, a new batch waits for the one slow batch while
   // the stages behind it have long finished (they sat idle 40 % of the time at thirteen stages).  If none is free the
-  // HOST waits for one (a few hundred microseconds at the bench's load): what the batch needs from the engine stream
-  // is enqueued before the wait, so the search starts the moment a stage frees up -- enqueued blindly behind "the
-  // oldest", as in round 2, a stage's stream sat idle 7 ms between two searches of 23 ms.
-  int slot = 0;
-  g_trace.start();
-  if (a.depth > 1) {
-    static const bool nowait = getenv("RNA_ASTAR_NOWAIT") != nullptr;   // developer knob: the round-2 behaviour
-    // A stage known to be free is taken without asking anybody; otherwise the stages are asked in the order of their launches
-    // (they end roughly in that order), at most RNA_ASTAR_QUERIES_PER_LOOK (3) per look, and the first one found complete is
-    // taken.  (Round 6 measured this loop, RNA_HOST_TRACE=1: the host spends 1.38 ms of a 1.57 ms pass here -- not in the
-    // queries, which cost 5 us each, but because every stage IS taken: a stage's cycle is 4.5 ms from enqueue until its search
-    // may start (the pass's map-update chain, snapshot and launch order), 22.4 ms of search and 1 ms until the host has
-    // noticed; a completion flag written by the stream instead of the event changes nothing.)
-    static const int per_look = getenv("RNA_ASTAR_QUERIES_PER_LOOK") ? std::max(1, atoi(getenv("RNA_ASTAR_QUERIES_PER_LOOK"))) : 3;   // developer knob
-    for (int spin = 0;; ++spin) {
-      int best = -1, oldest = 0;
-      for (int d = 0; d < a.depth; ++d) {
-        if (a.stage_seq[d] < a.stage_seq[oldest]) oldest = d;
-        if (!a.busy[d] && (best < 0 || a.stage_seq[d] < a.stage_seq[best])) best = d;
-      }
-      if (best < 0) {
-        // the busy stages by age; every eighth look asks all of them (a batch with one very long search must not hide the others)
-        int order[AstarDevice::MAX_DEPTH], nb = 0;
-        for (int d = 0; d < a.depth; ++d) if (a.busy[d]) order[nb++] = d;
-        std::sort(order, order + nb, [&](int x, int y) { return a.stage_seq[x] < a.stage_seq[y]; });
-        const int ask = (spin & 7) == 7 ? nb : std::min(nb, per_look);
-        for (int k = 0; k < ask && best < 0; ++k) {
-          const int d = order[k];
-          g_trace.queries += 1;
-          const hipError_t q = hipEventQuery(a.done[d]);
-          if (q == hipSuccess) {
-            int rc = RNA_OK;
-            if (stage_settled(e, d, &rc)) { a.busy[d] = false; best = d; }
-            if (g_trace.on && g_stage.armed[d] && best == d) {
-              float f = 0;
-              if (hipEventElapsedTime(&f, g_stage.a[d], g_stage.c[d]) == hipSuccess) {
-                g_stage.gpu_ms += f; g_stage.n += 1;
-                g_stage.host_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g_stage.t_enq[d]).count();
-              }
-              g_stage.armed[d] = false;
-            }
-            if (rc != RNA_OK) return rc;
-          } else {
-            (void)hipGetLastError();   // hipErrorNotReady is not an error
-          }
-        }
-      }
-      if (best >= 0) { slot = best; break; }
-      if (nowait) { slot = oldest; break; }
-      // (no stage free: the host SLEEPS between looks -- with thirteen launches in flight a stage that frees up 50 us before
-      // the host notices costs nothing, and eight ranks of one node share the host's cores; round 5 yielded 64 times and then
-      // slept 20 us, which kept a core busy: config.host_cores_used 0.98)
-      static const int wait_us = getenv("RNA_ASTAR_WAIT_US") ? atoi(getenv("RNA_ASTAR_WAIT_US")) : 50;   // developer knob
-      if (spin >= 2 && wait_us > 0) std::this_thread::sleep_for(std::chrono::microseconds(wait_us));
-      else std::this_thread::yield();
+  // HOST waits for one (a few hundred microseconds at the bench's load) -- enqueued blindly behind "the oldest", as in
+  // round 2, a stage's stream sat idle 7 ms between two searches of 23 ms.
+  static const bool nowait = getenv("RNA_ASTAR_NOWAIT") != nullptr;   // developer knob: the round-2 behaviour
+  // A stage known to be free is taken without asking anybody; otherwise the stages are asked in the order of their launches
+  // (they end roughly in that order), at most RNA_ASTAR_QUERIES_PER_LOOK (3) per look, and the first one found complete is
+  // taken.  (Round 6 measured this loop, RNA_HOST_TRACE=1: the host spends 1.38 ms of a 1.57 ms pass here -- not in the
+  // queries, which cost 5 us each, but because every stage IS taken: a stage's cycle is 4.5 ms from enqueue until its search
+  // may start (the pass's map-update chain, snapshot and launch order), 22.4 ms of search and 1 ms until the host has
+  // noticed; a completion flag written by the stream instead of the event changes nothing.)
+  static const int per_look = getenv("RNA_ASTAR_QUERIES_PER_LOOK") ? std::max(1, atoi(getenv("RNA_ASTAR_QUERIES_PER_LOOK"))) : 3;   // developer knob
+  int slot = -1;
+  for (int spin = 0; slot < 0; ++spin) {
+    int oldest = 0;
+    for (int d = 0; d < a.depth; ++d) {
+      if (a.stage[d].seq < a.stage[oldest].seq) oldest = d;
+      if (!a.stage[d].busy && (slot < 0 || a.stage[d].seq < a.stage[slot].seq)) slot = d;
     }
-    g_trace.lap(0);
-    // the ring entry this launch writes: the batch that read it 2 x depth launches ago is over and settled
-    const unsigned long long prev = a.launches + 1 >= (unsigned long long)a.ring_n ? a.launches + 1 - (unsigned long long)a.ring_n : 0;
-    if (prev > 0)
-      for (int d = 0; d < a.depth; ++d)
-        if (a.busy[d] && a.stage_seq[d] == prev) {
-          int rc = RNA_OK;
-          do { RNA_HIP(e, hipEventSynchronize(a.done[d])); } while (!stage_settled(e, d, &rc) && rc == RNA_OK);
-          if (rc != RNA_OK) return rc;
-          a.busy[d] = false;
+    if (slot < 0) {
+      // the busy stages by age; every eighth look asks all of them (a batch with one very long search must not hide the others)
+      int order[AstarDevice::MAX_DEPTH], nb = 0;
+      for (int d = 0; d < a.depth; ++d) if (a.stage[d].busy) order[nb++] = d;
+      std::sort(order, order + nb, [&](int x, int y) { return a.stage[x].seq < a.stage[y].seq; });
+      const int ask = (spin & 7) == 7 ? nb : std::min(nb, per_look);
+      for (int k = 0; k < ask && slot < 0; ++k) {
+        const int d = order[k];
+        g_trace.queries += 1;
+        if (hipEventQuery(a.stage[d].done) != hipSuccess) { (void)hipGetLastError(); continue; }   // hipErrorNotReady is not an error
+        bool sent = false;
+        RNA_TRY(stage_settled(e, d, &sent));
+        if (sent) continue;   // a second pass went out: the stage stays busy
+        a.stage[d].busy = false;
+        slot = d;
+        if (g_trace.on && g_stage.armed[d]) {
+          float f = 0;
+          if (hipEventElapsedTime(&f, g_stage.a[d], g_stage.c[d]) == hipSuccess) {
+            g_stage.gpu_ms += f; g_stage.n += 1;
+            g_stage.host_busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g_stage.t_enq[d]).count();
+          }
+          g_stage.armed[d] = false;
         }
+      }
+    }
+    if (slot >= 0) break;
+    if (nowait) { slot = oldest; break; }
+    // (no stage free: the host SLEEPS between looks -- with thirteen launches in flight a stage that frees up 50 us before
+    // the host notices costs nothing, and eight ranks of one node share the host's cores; round 5 yielded 64 times and then
+    // slept 20 us, which kept a core busy: config.host_cores_used 0.98)
+    static const int wait_us = getenv("RNA_ASTAR_WAIT_US") ? atoi(getenv("RNA_ASTAR_WAIT_US")) : 50;   // developer knob
+    if (spin >= 2 && wait_us > 0) std::this_thread::sleep_for(std::chrono::microseconds(wait_us));
+    else std::this_thread::yield();
   }
+  g_trace.lap(0);
+  // the ring entry this launch writes: the batch that read it 2 x depth launches ago is over and settled
+  const unsigned long long prev = a.launches + 1 >= (unsigned long long)a.ring_n ? a.launches + 1 - (unsigned long long)a.ring_n : 0;
+  for (int d = 0; prev > 0 && d < a.depth; ++d)
+    if (a.stage[d].busy && a.stage[d].seq == prev) RNA_TRY(stage_wait(e, d));
+  *slot_out = slot;
+  return RNA_OK;
+}
+
+// One batch (<= max_queries) on the stage pick_stage chose, or on the engine stream.  Pipelined, the mask snapshot and the launch
+// order go to the side stream, behind an event of the engine stream and into an entry of the launch ring (whatever changes the
+// masks next waits for the snapshot: side_join) -- on the stage's own stream these two short kernels waited up to a millisecond
+// for CU slots among the searches' workgroups, and the engine stream's next map update with them --, then the search to the
+// stage's stream.  The order of the calls below is the contract of a pipelined launch.
+int launch_chunk(rna_engine* e, const rna_astar_query* q_dev, int n, int32_t* paths_dev, int max_len,
+                 rna_astar_result* res_dev, int* slot_out) {
+  AstarDevice& a = e->astar;
+  const bool pipelined = a.depth > 1;
+  int slot = 0, r = -1;
+  g_trace.start();
+  if (pipelined) RNA_TRY(pick_stage(e, &slot));
   g_trace.lap(1);
-  if (a.depth == 1 && a.retry_armed[0]) {   // one stream: the batch before this one has to be complete before its slots are reused
-    RNA_HIP(e, hipStreamSynchronize(e->stream));
-    int rc = RNA_OK;
-    (void)stage_settled(e, 0, &rc);
-    if (rc != RNA_OK) return rc;
+  if (!pipelined && stage_pending(a, 0)) RNA_TRY(stage_wait(e, 0));   // one stream: the batch before this one has to be complete before its slots are reused
+  AstarStage& s = a.stage[slot];
+  hipStream_t search = stage_stream(e, slot), prep = search;
+  if (pipelined) {
+    if (s.busy) RNA_HIP(e, hipStreamWaitEvent(search, s.done, 0));   // (RNA_ASTAR_NOWAIT only; the same stream anyway)
+    if (g_trace.on) {
+      if (!g_stage.a[slot]) { (void)hipEventCreate(&g_stage.a[slot]); (void)hipEventCreate(&g_stage.c[slot]); }
+      (void)hipEventRecord(g_stage.a[slot], search);
+      g_stage.t_enq[slot] = std::chrono::steady_clock::now();
+    }
+    r = (int)(a.launches % (unsigned long long)a.ring_n);
+    RNA_TRY(side_stream(e, &prep));
+    RNA_HIP(e, hipEventRecord(a.ev_init, e->stream));
+    RNA_HIP(e, hipStreamWaitEvent(prep, a.ev_init, 0));
+    if (a.ring[r].used) RNA_HIP(e, hipStreamWaitEvent(prep, a.ring[r].free, 0));   // (thirteen launches ago at least: long over)
   }
-  hipStream_t search_stream = a.depth > 1 ? a.side[slot] : e->stream;
-  if (a.depth > 1 && a.busy[slot]) RNA_HIP(e, hipStreamWaitEvent(search_stream, a.done[slot], 0));   // (RNA_ASTAR_NOWAIT only; the same stream anyway)
-  if (g_trace.on && a.depth > 1) {
-    if (!g_stage.a[slot]) { (void)hipEventCreate(&g_stage.a[slot]); (void)hipEventCreate(&g_stage.c[slot]); }
-    (void)hipEventRecord(g_stage.a[slot], search_stream);
-    g_stage.t_enq[slot] = std::chrono::steady_clock::now();
+  RNA_TRY(tsa_snapshot(e, slot, r, prep));
+  if (pipelined) {
+    RNA_HIP(e, hipEventRecord(s.snap_done, prep));
+    s.snap_pending = true;
   }
-  {
-    int rc = tsa_launch(e, slot, e->stream, search_stream, a.depth > 1 ? a.ev_init : nullptr, q_dev, n, paths_dev, max_len, res_dev);
-    if (rc != RNA_OK) return rc;
+  RNA_TRY(tsa_order(e, slot, r, prep, q_dev, n));
+  if (pipelined) {
+    RNA_HIP(e, hipEventRecord(a.ev_prep, prep));
+    RNA_HIP(e, hipStreamWaitEvent(search, a.ev_prep, 0));
   }
-  if (g_trace.on && a.depth > 1) { (void)hipEventRecord(g_stage.c[slot], search_stream); g_stage.armed[slot] = true; }
+  if (s.retry_flag) *s.retry_flag = 0;
+  RNA_TRY(tsa_search(e, slot, r, search, q_dev, n, paths_dev, max_len, res_dev));
+  // the count of searches to repeat travels to pinned host memory behind the search (before the stage's `done` event)
+  if (s.retry_armed) RNA_HIP(e, hipMemcpyAsync(s.retry_flag, tsa_retry_count(e, slot), sizeof(int), hipMemcpyDeviceToHost, search));
+  if (pipelined) {
+    RNA_HIP(e, hipEventRecord(a.ring[r].free, search));
+    a.ring[r].used = true;
+    if (g_trace.on) { (void)hipEventRecord(g_stage.c[slot], search); g_stage.armed[slot] = true; }
+  }
   g_trace.lap(2);
-  if (a.depth > 1) {
-    RNA_HIP(e, hipEventRecord(a.done[slot], search_stream));
-    a.busy[slot] = true;
+  if (pipelined) {
+    RNA_HIP(e, hipEventRecord(s.done, search));
+    s.busy = true;
   }
   a.launches += 1;
-  a.stage_seq[slot] = a.launches;
-  a.last_queries = q_dev;
-  a.last_results = res_dev;
-  a.last_n = n;
-  a.last_slot = slot;
+  s.seq = a.launches;
+  a.last_queries = q_dev; a.last_results = res_dev; a.last_n = n; a.last_slot = slot;
   if (slot_out) *slot_out = slot;
   g_trace.lap(3);
-  if (a.depth > 1) g_trace.n += 1;
+  if (pipelined) g_trace.n += 1;
   return RNA_OK;
 }
 
@@ -343,18 +368,8 @@ void tsa_stats_dump();
 // every stream is idle (sync_all): second passes that are due go out and are waited for
 int astar_settle(rna_engine* e) {
   AstarDevice& a = e->astar;
-  if (a.depth == 1 && a.retry_armed[0]) {
-    int rc = RNA_OK;
-    if (!stage_settled(e, 0, &rc) && rc == RNA_OK) RNA_HIP(e, hipStreamSynchronize(e->stream));
-    return rc;
-  }
-  for (int d = 0; d < a.depth && d < AstarDevice::MAX_DEPTH; ++d) {
-    if (!a.busy[d]) continue;
-    int rc = RNA_OK;
-    while (!stage_settled(e, d, &rc) && rc == RNA_OK) RNA_HIP(e, hipStreamSynchronize(a.side[d]));
-    if (rc != RNA_OK) return rc;
-    a.busy[d] = false;
-  }
+  for (int d = 0; d < a.depth && d < AstarDevice::MAX_DEPTH; ++d)
+    if (stage_pending(a, d)) RNA_TRY(stage_wait(e, d));
   return RNA_OK;
 }
 int astar_release(rna_engine* e) {
@@ -365,27 +380,16 @@ int astar_release(rna_engine* e) {
 #ifdef RNA_TSA_STATS
   tsa_stats_dump();
 #endif
-  for (int d = 0; d < AstarDevice::MAX_DEPTH; ++d) {
-    dev_free(&a.g[d]); dev_free(&a.rev[d]);
-    if (a.tsa_aux[d]) { (void)hipFree(a.tsa_aux[d]); a.tsa_aux[d] = nullptr; }
-    dev_free(&a.g_retry[d]);
-    if (a.tsa_aux_retry[d]) { (void)hipFree(a.tsa_aux_retry[d]); a.tsa_aux_retry[d] = nullptr; }
-    if (a.side[d]) { (void)hipStreamDestroy(a.side[d]); a.side[d] = nullptr; }
-    if (a.done[d]) { (void)hipEventDestroy(a.done[d]); a.done[d] = nullptr; }
-    if (a.snap_done[d]) { (void)hipEventDestroy(a.snap_done[d]); a.snap_done[d] = nullptr; }
-    a.snap_pending[d] = false;
-    a.busy[d] = false;
-  }
+  for (AstarStage& s : a.stage) free_stage(s);
   if (a.ev_init) { (void)hipEventDestroy(a.ev_init); a.ev_init = nullptr; }
   if (a.ev_prep) { (void)hipEventDestroy(a.ev_prep); a.ev_prep = nullptr; }
-  for (int r = 0; r < AstarDevice::MAX_RING; ++r) {
-    if (a.ring_free[r]) { (void)hipEventDestroy(a.ring_free[r]); a.ring_free[r] = nullptr; }
-    a.ring_used[r] = false;
+  for (AstarRingEntry& r : a.ring) {
+    if (r.free) (void)hipEventDestroy(r.free);
+    r = AstarRingEntry{};
   }
   dev_free(&a.ring_mem);
   a.ring_n = 0;
   if (a.retry_flag) { (void)hipHostFree(a.retry_flag); a.retry_flag = nullptr; }
-  for (int d = 0; d < AstarDevice::MAX_DEPTH; ++d) a.retry_armed[d] = false;
   dev_free(&a.queries_dev); dev_free(&a.results_dev); dev_free(&a.paths_dev);
   a.paths_cap = 0;
   a.last_queries = nullptr; a.last_results = nullptr; a.last_n = 0;
@@ -404,8 +408,7 @@ extern "C" int rna_astar_configure(rna_engine* e, int max_queries, int queue_cap
     const int dd = atoi(d);
     if (dd >= 1 && dd != a.depth) { astar_release(e); a.depth = dd; }
   }
-  if (max_queries) a.max_queries = max_queries;
-  if (queue_capacity) a.queue_cap = queue_capacity;
+  if (max_queries) a.max_queries = max_queries;   // (queue_capacity: of the ABI, no longer used)
   if (bucket_width) a.bucket_width = bucket_width;
   return RNA_OK;
 }
@@ -425,7 +428,7 @@ extern "C" int rna_astar_set_pipeline_depth(rna_engine* e, int depth) {
 extern "C" int rna_astar_effective_config(const rna_engine* e, int* pipeline_depth, int* pages_per_query, int* max_queries) {
   if (!e) return RNA_EINVAL;
   const AstarDevice& a = e->astar;
-  const bool live = a.g[0] != nullptr;
+  const bool live = a.live();
   if (pipeline_depth) *pipeline_depth = live ? a.depth : 0;
   if (pages_per_query) *pages_per_query = live ? a.page_cap : 0;
   if (max_queries) *max_queries = live ? a.max_queries : 0;
@@ -482,17 +485,7 @@ extern "C" int rna_astar_batch(rna_engine* e, const rna_astar_query* queries_hos
     int slot = 0;
     rc = launch_chunk(e, a.queries_dev, m, a.paths_dev, max_path_len, a.results_dev, &slot);
     if (rc != RNA_OK) return rc;
-    if (a.depth > 1) {
-      int src = RNA_OK;
-      do { RNA_HIP(e, hipEventSynchronize(a.done[slot])); } while (!stage_settled(e, slot, &src) && src == RNA_OK);
-      if (src != RNA_OK) return src;
-      a.busy[slot] = false;
-    } else if (a.retry_armed[0]) {
-      RNA_HIP(e, hipStreamSynchronize(e->stream));
-      int src = RNA_OK;
-      (void)stage_settled(e, 0, &src);   // (a second pass, if one is due, is on the stream ahead of the copies below)
-      if (src != RNA_OK) return src;
-    }
+    if (stage_pending(a, slot) && (rc = stage_wait(e, slot)) != RNA_OK) return rc;
     RNA_HIP(e, hipMemcpyAsync(results_host + o, a.results_dev, (size_t)m * sizeof(rna_astar_result),
                               hipMemcpyDeviceToHost, e->stream));
     RNA_HIP(e, hipMemcpyAsync(paths_host + (size_t)o * max_path_len, a.paths_dev,
@@ -515,7 +508,7 @@ extern "C" int rna_astar_download_nbr_mask(rna_engine* e, uint8_t* host, size_t 
 extern "C" int rna_astar_job_counters(rna_engine* e, uint64_t* counters_host, int reset) {
   if (!e || !counters_host) return RNA_EINVAL;
   AstarDevice& a = e->astar;
-  if (!a.g[0]) return fail(e, RNA_ESTATE, "no A* batch has run yet");
+  if (!a.live()) return fail(e, RNA_ESTATE, "no A* batch has run yet");
   RNA_ENTER(e);
   int rc = sync_all(e);
   if (rc != RNA_OK) return rc;
@@ -528,7 +521,7 @@ extern "C" int rna_astar_job_counters(rna_engine* e, uint64_t* counters_host, in
 extern "C" int rna_astar_settled_counts(rna_engine* e, int32_t* counts_host, int n) {
   if (!e || !counts_host || n <= 0) return RNA_EINVAL;
   AstarDevice& a = e->astar;
-  if (!a.g[0] || !a.last_queries || n != a.last_n) return fail(e, RNA_ESTATE, "no resident A* batch of that size");
+  if (!a.live() || !a.last_queries || n != a.last_n) return fail(e, RNA_ESTATE, "no resident A* batch of that size");
   RNA_ENTER(e);
   int32_t* d_counts = nullptr;
   int rc = sync_all(e);

@@ -51,7 +51,7 @@ constexpr int TSA_WAVES = 8;          // wavefronts per workgroup = per query wh
 constexpr int TSA_WAVES_PER_EU = 8;   // eight wavefronts per SIMD: the kernel must fit 64 VGPRs
 constexpr int TSA_HPASS = 4;          // one-cell passes along a row that is still moving before it goes to the scan (3 / 4 / 5 -> 144.1 / 144.0 / 143.6 k, the means of the two runs in profiles/r04_ab_row_scan_passes_first.txt)
 constexpr int TSA_IDLE_SLEEP = 4;     // an idle wavefront looks at the entry counter every 64 x this many clocks (1 / 4 / 12: profiles/r05_ab_idle_sleep.txt)
-constexpr int TSA_PRIO_FIRST = 0;     // the first this many workgroups of a pipelined batch to start run at raised wave priority (tsa_launch)
+constexpr int TSA_PRIO_FIRST = 0;     // the first this many workgroups of a pipelined batch to start run at raised wave priority (tsa_search)
 constexpr int TSA_BT_PRIO = 3;        // issue priority of the wavefront that traces the path (1.05 instead of 2.0 ms per path: profiles/r05_ab_backtrace_priority.txt)
 constexpr int TSA_SCOPE = __HIP_MEMORY_SCOPE_AGENT;   // scope the loads of the search field are coherent at: every load goes to L2 (sc1), see ld_l2
 constexpr int TSA_MAX_TILE_WORDS = 2048;   // active-tile bitset words -> up to 65536 tiles
@@ -1797,69 +1797,94 @@ bool tsa_supported(const rna_engine* e) { return (size_t)tsa_ntile(e) <= (size_t
 int tsa_tiles(const rna_engine* e) { return tsa_ntile(e); }
 // HBM of one pipeline stage: pages and their edge-column copies (cap per query + the shared page 0) ...
 size_t tsa_pool_bytes(int max_queries, int cap) { return (size_t)max_queries * ((size_t)cap + 1) * (TILE_WORDS + AUX_WORDS) * sizeof(unsigned); }
-// ... and one allocation that must start zeroed: ticket | nalloc | perm | mask snapshot | tmap | owner
-size_t tsa_aux_bytes(const rna_engine* e, int max_queries, int cap) {
-  const size_t ntile = (size_t)tsa_ntile(e);
-  return 256 + 2 * tsa_align256((size_t)max_queries * sizeof(int)) + tsa_align256(ntile * MASK_STRIDE) +
-         tsa_align256((size_t)max_queries * ntile * sizeof(unsigned)) + tsa_align256((size_t)max_queries * ((size_t)cap + 1) * sizeof(unsigned));
+size_t tsa_retry_pool_bytes(const rna_engine* e) { return tsa_pool_bytes(TSA_RETRY, tsa_ntile(e)); }   // TSA_RETRY slots with a page per tile
+
+// ... and three kinds of block whose layout the host decides.  Each layout is written down ONCE, in the function that returns
+// its offsets and its total; the sizes, the views and the accessors below read that.  Every block begins with a head of 256 bytes:
+// the ticket at 0, in a retry block the query each retry slot served (-1: none) and behind them the number of searches to repeat,
+// and in the head's second half the kernels' counters -- directly in front of the page counts, where tsa_counters_of looks.
+constexpr size_t TSA_HEAD = 256, TSA_HEAD_SERVED = 8 * sizeof(int), TSA_HEAD_COUNT = TSA_HEAD_SERVED + TSA_RETRY * sizeof(int),
+                 TSA_HEAD_COUNTERS = TSA_HEAD - TSA_COUNTER_WORDS * sizeof(unsigned long long);
+static_assert(TSA_HEAD_COUNT + sizeof(int) <= TSA_HEAD_COUNTERS, "the two halves of a block's head do not overlap");
+struct TsaCursor {   // the parts behind the head, one after the other, each padded to 256 bytes
+  size_t at = TSA_HEAD;
+  size_t take(size_t bytes) { const size_t o = at; at += tsa_align256(bytes); return o; }
+};
+// (the braced lists below are evaluated left to right: the order of the members IS the order in memory, `total` comes last)
+struct TsaStageBlock { size_t nalloc, perm, nbr_tm, tmap, owner, total; };   // a stage's block; it must start zeroed
+static TsaStageBlock tsa_stage_block(const rna_engine* e) {
+  const size_t nq = (size_t)e->astar.max_queries, ntile = (size_t)tsa_ntile(e), cap = (size_t)e->astar.page_cap;
+  TsaCursor c;
+  return {c.take(nq * sizeof(int)), c.take(nq * sizeof(int)), c.take(ntile * MASK_STRIDE), c.take(nq * ntile * sizeof(unsigned)),
+          c.take(nq * (cap + 1) * sizeof(unsigned)), c.at};
 }
-static TsaStage tsa_stage_view(const rna_engine* e, int slot) {
+struct TsaRetryBlock { size_t nalloc, tmap, owner, list, total; };   // the block of a stage's retry slots (zeroed too); list: the searches to repeat
+static TsaRetryBlock tsa_retry_block(const rna_engine* e) {
+  const size_t nq = (size_t)e->astar.max_queries, ntile = (size_t)tsa_ntile(e);
+  TsaCursor c;
+  return {c.take(TSA_RETRY * sizeof(int)), c.take(TSA_RETRY * ntile * sizeof(unsigned)), c.take(TSA_RETRY * (ntile + 1) * sizeof(unsigned)),
+          c.take(nq * sizeof(int)), c.at};
+}
+struct TsaRingBlock { size_t perm, nbr_tm, total; };   // one entry of the launch ring (AstarDevice::ring_mem)
+static TsaRingBlock tsa_ring_block(const rna_engine* e) {
+  TsaCursor c;
+  return {c.take((size_t)e->astar.max_queries * sizeof(int)), c.take((size_t)tsa_ntile(e) * MASK_STRIDE), c.at};
+}
+size_t tsa_stage_bytes(const rna_engine* e) { return tsa_stage_block(e).total; }
+size_t tsa_retry_bytes(const rna_engine* e) { return tsa_retry_block(e).total; }
+size_t tsa_ring_bytes(const rna_engine* e) { return tsa_ring_block(e).total; }
+template <typename T>
+static T* tsa_at(char* block, size_t offset) { return reinterpret_cast<T*>(block + offset); }
+
+static TsaStage tsa_stage_view(const rna_engine* e, int d) {
   const AstarDevice& a = e->astar;
-  const size_t ntile = (size_t)tsa_ntile(e);
-  char* base = static_cast<char*>(a.tsa_aux[slot]);
+  const AstarStage& s = a.stage[d];
+  const TsaStageBlock L = tsa_stage_block(e);
   TsaStage S;
   S.cap = a.page_cap;
-  S.pages = reinterpret_cast<unsigned*>(a.g[slot]);
+  S.pages = s.pool;
   S.paux = S.pages + (((size_t)a.max_queries * ((size_t)S.cap + 1)) << 10);
-  S.ticket = reinterpret_cast<int*>(base);
-  base += 256;
-  S.nalloc = reinterpret_cast<int*>(base);
-  base += tsa_align256((size_t)a.max_queries * sizeof(int));
-  S.perm = reinterpret_cast<int*>(base);
-  base += tsa_align256((size_t)a.max_queries * sizeof(int));
-  S.nbr_tm = reinterpret_cast<uint8_t*>(base);
-  base += tsa_align256(ntile * MASK_STRIDE);
-  S.tmap = reinterpret_cast<unsigned*>(base);
-  base += tsa_align256((size_t)a.max_queries * ntile * sizeof(unsigned));
-  S.owner = reinterpret_cast<unsigned*>(base);
+  S.ticket = tsa_at<int>(s.block, 0);
+  S.nalloc = tsa_at<int>(s.block, L.nalloc);
+  S.perm = tsa_at<int>(s.block, L.perm);
+  S.nbr_tm = tsa_at<uint8_t>(s.block, L.nbr_tm);
+  S.tmap = tsa_at<unsigned>(s.block, L.tmap);
+  S.owner = tsa_at<unsigned>(s.block, L.owner);
   return S;
 }
-// The retry view of a stage (see TsaLaunch::retry): TSA_RETRY slots with one page per tile; its own pages and
-// ticket | nalloc | tmap | owner block, the mask snapshot of the stage itself.
-size_t tsa_retry_pool_bytes(const rna_engine* e) { return tsa_pool_bytes(TSA_RETRY, tsa_ntile(e)); }
-size_t tsa_retry_aux_bytes(const rna_engine* e) {
-  const size_t ntile = (size_t)tsa_ntile(e);
-  return 256 + tsa_align256(TSA_RETRY * sizeof(int)) + tsa_align256((size_t)TSA_RETRY * ntile * sizeof(unsigned)) +
-         tsa_align256((size_t)TSA_RETRY * (ntile + 1) * sizeof(unsigned)) + tsa_align256((size_t)e->astar.max_queries * sizeof(int));
+// what a batch on stage d reads: pipelined, its ticket, launch order and mask snapshot are those of a ring entry
+static TsaStage tsa_launch_view(const rna_engine* e, int d, int ring) {
+  TsaStage S = tsa_stage_view(e, d);
+  if (ring >= 0) {
+    const TsaRingBlock L = tsa_ring_block(e);
+    char* entry = e->astar.ring_mem + (size_t)ring * e->astar.ring_stride;
+    S.ticket = tsa_at<int>(entry, 0);
+    S.perm = tsa_at<int>(entry, L.perm);
+    S.nbr_tm = tsa_at<uint8_t>(entry, L.nbr_tm);
+  }
+  return S;
 }
-// the stage's list of searches to repeat (the last block of the retry aux)
-static int* tsa_retry_list(const rna_engine* e, int slot) {
-  const size_t ntile = (size_t)tsa_ntile(e);
-  return reinterpret_cast<int*>(static_cast<char*>(e->astar.tsa_aux_retry[slot]) + 256 + tsa_align256(TSA_RETRY * sizeof(int)) +
-                                tsa_align256((size_t)TSA_RETRY * ntile * sizeof(unsigned)) + tsa_align256((size_t)TSA_RETRY * (ntile + 1) * sizeof(unsigned)));
-}
-// [TSA_RETRY] ints in the retry view's ticket block: the query each retry slot served in the stage's current batch (-1: none)
-static int* tsa_retry_served(const rna_engine* e, int slot) { return reinterpret_cast<int*>(e->astar.tsa_aux_retry[slot]) + 8; }
-// the int behind them: searches of the stage's current batch that ended with status 5 (copied to pinned host memory
-// behind the search, so that the host sees it when the stage's stream is idle -- no PCIe atomics needed)
-static int* tsa_retry_count(const rna_engine* e, int slot) { return tsa_retry_served(e, slot) + TSA_RETRY; }
-static TsaStage tsa_retry_view(const rna_engine* e, int slot, const TsaStage& main) {
-  const AstarDevice& a = e->astar;
-  const size_t ntile = (size_t)tsa_ntile(e);
-  char* base = static_cast<char*>(a.tsa_aux_retry[slot]);
+// The retry view of a stage (see TsaLaunch::retry): its own pages, ticket, page counts and tables; the launch order and the
+// mask snapshot are the first pass's.
+static TsaStage tsa_retry_view(const rna_engine* e, int d, const TsaStage& main) {
+  const AstarStage& s = e->astar.stage[d];
+  const TsaRetryBlock L = tsa_retry_block(e);
   TsaStage S = main;
-  S.cap = (int)ntile;
-  S.pages = reinterpret_cast<unsigned*>(a.g_retry[slot]);
+  S.cap = tsa_ntile(e);
+  S.pages = s.retry_pool;
   S.paux = S.pages + (((size_t)TSA_RETRY * ((size_t)S.cap + 1)) << 10);
-  S.ticket = reinterpret_cast<int*>(base);
-  base += 256;
-  S.nalloc = reinterpret_cast<int*>(base);
-  base += tsa_align256(TSA_RETRY * sizeof(int));
-  S.tmap = reinterpret_cast<unsigned*>(base);
-  base += tsa_align256((size_t)TSA_RETRY * ntile * sizeof(unsigned));
-  S.owner = reinterpret_cast<unsigned*>(base);
+  S.ticket = tsa_at<int>(s.retry_block, 0);
+  S.nalloc = tsa_at<int>(s.retry_block, L.nalloc);
+  S.tmap = tsa_at<unsigned>(s.retry_block, L.tmap);
+  S.owner = tsa_at<unsigned>(s.retry_block, L.owner);
   return S;
 }
+// null where the stage has no retry slots.  The count is copied to pinned host memory behind the search, so that the host sees
+// it when the stage's stream is idle -- no PCIe atomics needed.
+static int* tsa_retry_served(const rna_engine* e, int d) { char* b = e->astar.stage[d].retry_block; return b ? tsa_at<int>(b, TSA_HEAD_SERVED) : nullptr; }
+int* tsa_retry_count(const rna_engine* e, int d) { char* b = e->astar.stage[d].retry_block; return b ? tsa_at<int>(b, TSA_HEAD_COUNT) : nullptr; }
+static int* tsa_retry_list(const rna_engine* e, int d) { char* b = e->astar.stage[d].retry_block; return b ? tsa_at<int>(b, tsa_retry_block(e).list) : nullptr; }
+
 int tsa_retry_prepare(rna_engine* e, int slot) {   // fresh retry slots: page 0 of each "unreached", the other pages as allocated
   const TsaStage S = tsa_retry_view(e, slot, tsa_stage_view(e, slot));
   hipLaunchKernelGGL(tsa_zero_page0_kernel, dim3(TSA_RETRY), dim3(256), 0, e->stream, S.pages, S.paux, S.cap);
@@ -1875,115 +1900,88 @@ int tsa_stage_prepare(rna_engine* e, int slot) {
   return RNA_OK;
 }
 
-// one entry of the launch ring (AstarDevice::ring_mem): ticket | launch order | mask snapshot
-size_t tsa_ring_bytes(const rna_engine* e, int max_queries) {
-  return 256 + tsa_align256((size_t)max_queries * sizeof(int)) + tsa_align256((size_t)tsa_ntile(e) * MASK_STRIDE);
-}
-static_assert(sizeof(TsaLaunch) <= sizeof(AstarDevice::last_launch[0]), "AstarDevice::last_launch holds a TsaLaunch");
+static_assert(sizeof(TsaLaunch) <= sizeof(AstarStage::last_launch), "AstarStage::last_launch holds a TsaLaunch");
 
 // the second pass over the stage's last batch (the searches that outgrew their share of pages, on the stage's full-size
 // retry slots; workgroups without such a query end at once)
-int tsa_retry_launch(rna_engine* e, int slot, hipStream_t search_stream, int count) {
-  AstarDevice& a = e->astar;
+int tsa_retry_launch(rna_engine* e, int d, hipStream_t st, int count) {
+  const AstarStage& s = e->astar.stage[d];
   TsaLaunch A;
-  memcpy(&A, a.last_launch[slot], sizeof(A));
+  memcpy(&A, s.last_launch, sizeof(A));
   A.retry = 1;
   A.retry_count = nullptr;
-  A.S2 = tsa_retry_view(e, slot, A.S);
+  A.S2 = tsa_retry_view(e, d, A.S);
   // TSA_RETRY searches at a time share the stage's retry slots: one launch after the other on the stage's stream
   for (int base = 0; base < count; base += TSA_RETRY) {
     A.retry_base = base;
     const int wgs = std::min(TSA_RETRY, count - base);
-    if (a.depth > 1) hipLaunchKernelGGL((tsa_search_kernel<TSA_WAVES, true>), dim3(wgs), dim3(TSA_WAVES * 64), a.last_lds[slot], search_stream, A);
-    else hipLaunchKernelGGL((tsa_search_kernel<16, true>), dim3(wgs), dim3(16 * 64), a.last_lds[slot], search_stream, A);
+    if (e->astar.depth > 1) hipLaunchKernelGGL((tsa_search_kernel<TSA_WAVES, true>), dim3(wgs), dim3(TSA_WAVES * 64), s.last_lds, st, A);
+    else hipLaunchKernelGGL((tsa_search_kernel<16, true>), dim3(wgs), dim3(16 * 64), s.last_lds, st, A);
     RNA_HIP(e, hipGetLastError());
   }
   return RNA_OK;
 }
 
-int tsa_launch(rna_engine* e, int slot, hipStream_t init_stream, hipStream_t search_stream, hipEvent_t ev_init,
-               const rna_astar_query* q_dev, int n, int32_t* paths_dev, int max_len, rna_astar_result* res_dev) {
-  AstarDevice& a = e->astar;
+struct TsaGrid { int rows, cols, ti, tj; };
+static TsaGrid tsa_grid(const rna_engine* e) {
   const int rows = e->geom.size[0], cols = e->geom.size[1];
-  const int ti = (rows + TI - 1) / TI, tj = (cols + TJ - 1) / TJ;
-  TsaStage S = tsa_stage_view(e, slot);
-  // Snapshot of the neighbour masks as they are NOW (a later map update must not disturb a search in flight) and the
-  // launch order of the batch.  Pipelined: into an entry of the launch ring, on the side stream behind an event of the
-  // engine stream (whatever changes the masks next waits for the snapshot, side_join) -- on the stage's own stream
-  // these two short kernels waited up to a millisecond for CU slots among the searches' workgroups, and the engine
-  // stream's next map update with them.  Single stream: in place.
-  hipStream_t prep_stream = search_stream;
-  int ring = -1;
-  if (ev_init) {
-    ring = (int)(a.launches % (unsigned long long)a.ring_n);
-    char* base = a.ring_mem + (size_t)ring * a.ring_stride;
-    S.ticket = reinterpret_cast<int*>(base);
-    S.perm = reinterpret_cast<int*>(base + 256);
-    S.nbr_tm = reinterpret_cast<uint8_t*>(base + 256 + tsa_align256((size_t)a.max_queries * sizeof(int)));
-    { const int rc = side_stream(e, &prep_stream); if (rc != RNA_OK) return rc; }
-    RNA_HIP(e, hipEventRecord(ev_init, init_stream));
-    RNA_HIP(e, hipStreamWaitEvent(prep_stream, ev_init, 0));
-    if (a.ring_used[ring]) RNA_HIP(e, hipStreamWaitEvent(prep_stream, a.ring_free[ring], 0));   // (thirteen launches ago at least: long over)
-  }
-  {
-    KernelTimer kt(e, RNA_K_ASTAR_INIT, prep_stream);
-    hipLaunchKernelGGL(tsa_snapshot_kernel, dim3(std::min(ti * tj, 4096)), dim3(256), 0, prep_stream, e->nbr, rows, cols, ti, tj, S.nbr_tm,
-                       e->geom.start[0], e->geom.start[1]);
-    RNA_HIP(e, hipGetLastError());
-  }
-  if (ev_init) {
-    RNA_HIP(e, hipEventRecord(a.snap_done[slot], prep_stream));
-    a.snap_pending[slot] = true;
-  }
-  {
-    // ticket and launch order (the tile map of a slot is reset by the workgroup that takes the slot)
-    KernelTimer kt(e, RNA_K_ASTAR_RESET, prep_stream);
-    const int ranked = n <= 2048 ? 1 : 0;
-    hipLaunchKernelGGL(tsa_prepare_kernel, dim3(1), dim3(256), ranked ? (size_t)n * sizeof(int) : 0, prep_stream, S, q_dev, n, rows, cols, ranked,
-                       a.g_retry[slot] ? tsa_retry_served(e, slot) : nullptr);
-    RNA_HIP(e, hipGetLastError());
-  }
-  if (ev_init) {
-    RNA_HIP(e, hipEventRecord(a.ev_prep, prep_stream));
-    RNA_HIP(e, hipStreamWaitEvent(search_stream, a.ev_prep, 0));
-  }
-  {
-    KernelTimer kt(e, RNA_K_ASTAR_SEARCH, search_stream);
-    const size_t nt_bytes = (size_t)((ti * tj + 31) / 32) * sizeof(unsigned);
-    TsaLaunch A;
-    memset(&A, 0, sizeof(A));
-    A.rows = rows; A.cols = cols; A.tiles_i = ti; A.tiles_j = tj; A.s0 = e->geom.start[0]; A.s1 = e->geom.start[1];
-    A.queries = q_dev; A.S = S; A.bucket_width = a.bucket_width; A.paths = paths_dev; A.max_path_len = max_len;
-    A.rev_all = a.rev[slot]; A.rev_cap = a.rev_cap; A.results = res_dev;
-    A.retry = 0; A.n = n; A.S2 = S;
-    A.prio_first = a.depth > 1 ? TSA_PRIO_FIRST : 0;
-    if (const char* pf = getenv("RNA_TSA_PRIO_FIRST")) A.prio_first = atoi(pf);   // developer knob
-    size_t lds_dyn = 4 * nt_bytes;
-    if (const char* pad = getenv("RNA_TSA_LDS_PAD")) lds_dyn += (size_t)atoi(pad);   // developer knob: fewer search workgroups per CU
-    // a search that outgrows its share of pages is searched again when the host sees the count (astar_settle)
-    const bool can_retry = a.g_retry[slot] != nullptr && a.retry_flag != nullptr;
-    A.retry_count = can_retry ? tsa_retry_count(e, slot) : nullptr;
-    A.retry_list = can_retry ? tsa_retry_list(e, slot) : nullptr;
-    A.retry_base = 0;
-    if (can_retry) a.retry_flag[slot] = 0;
-    a.last_retried[slot] = 0;
-    // 16 wavefronts per query where latency counts (one stream, or a batch too small to fill the chip: a lone search
-    // takes 9.1 instead of 12.9 ms), 8 where throughput does (16 in the pipeline: 91.6 k instead of 122.8 k cycles/s)
-    static const bool wide_env = getenv("RNA_TSA_WIDE") != nullptr;   // developer knob: 16 wavefronts per query always
-    const bool wide = wide_env || n <= 32;
-    if (a.depth > 1 && !wide) hipLaunchKernelGGL((tsa_search_kernel<TSA_WAVES, false>), dim3(n), dim3(TSA_WAVES * 64), lds_dyn, search_stream, A);
-    else hipLaunchKernelGGL((tsa_search_kernel<16, false>), dim3(n), dim3(16 * 64), lds_dyn, search_stream, A);
-    RNA_HIP(e, hipGetLastError());
-    memcpy(a.last_launch[slot], &A, sizeof(A));
-    a.last_lds[slot] = lds_dyn;
-    a.retry_armed[slot] = A.retry_count != nullptr;
-    // the count travels to pinned host memory behind the search (before the stage's `done` event)
-    if (A.retry_count) RNA_HIP(e, hipMemcpyAsync(a.retry_flag + slot, A.retry_count, sizeof(int), hipMemcpyDeviceToHost, search_stream));
-  }
-  if (ring >= 0) {
-    RNA_HIP(e, hipEventRecord(a.ring_free[ring], search_stream));
-    a.ring_used[ring] = true;
-  }
+  return {rows, cols, (rows + TI - 1) / TI, (cols + TJ - 1) / TJ};
+}
+// Snapshot of the neighbour masks as they are NOW: a later map update must not disturb a search in flight.
+int tsa_snapshot(rna_engine* e, int d, int ring, hipStream_t st) {
+  const TsaGrid G = tsa_grid(e);
+  KernelTimer kt(e, RNA_K_ASTAR_INIT, st);
+  hipLaunchKernelGGL(tsa_snapshot_kernel, dim3(std::min(G.ti * G.tj, 4096)), dim3(256), 0, st, e->nbr, G.rows, G.cols, G.ti, G.tj,
+                     tsa_launch_view(e, d, ring).nbr_tm, e->geom.start[0], e->geom.start[1]);
+  RNA_HIP(e, hipGetLastError());
+  return RNA_OK;
+}
+// ticket and launch order of the batch (the tile map of a slot is reset by the workgroup that takes the slot)
+int tsa_order(rna_engine* e, int d, int ring, hipStream_t st, const rna_astar_query* q_dev, int n) {
+  const TsaGrid G = tsa_grid(e);
+  KernelTimer kt(e, RNA_K_ASTAR_RESET, st);
+  const int ranked = n <= 2048 ? 1 : 0;
+  hipLaunchKernelGGL(tsa_prepare_kernel, dim3(1), dim3(256), ranked ? (size_t)n * sizeof(int) : 0, st, tsa_launch_view(e, d, ring), q_dev, n, G.rows,
+                     G.cols, ranked, tsa_retry_served(e, d));
+  RNA_HIP(e, hipGetLastError());
+  return RNA_OK;
+}
+// The search itself; the stage remembers the launch for its second passes (tsa_retry_launch) and for tsa_settled.
+int tsa_search(rna_engine* e, int d, int ring, hipStream_t st, const rna_astar_query* q_dev, int n, int32_t* paths_dev, int max_len,
+               rna_astar_result* res_dev) {
+  AstarDevice& a = e->astar;
+  AstarStage& s = a.stage[d];
+  const TsaGrid G = tsa_grid(e);
+  const TsaStage S = tsa_launch_view(e, d, ring);
+  KernelTimer kt(e, RNA_K_ASTAR_SEARCH, st);
+  const size_t nt_bytes = (size_t)((G.ti * G.tj + 31) / 32) * sizeof(unsigned);
+  TsaLaunch A;
+  memset(&A, 0, sizeof(A));
+  A.rows = G.rows; A.cols = G.cols; A.tiles_i = G.ti; A.tiles_j = G.tj; A.s0 = e->geom.start[0]; A.s1 = e->geom.start[1];
+  A.queries = q_dev; A.S = S; A.bucket_width = a.bucket_width; A.paths = paths_dev; A.max_path_len = max_len;
+  A.rev_all = s.rev; A.rev_cap = a.rev_cap; A.results = res_dev;
+  A.retry = 0; A.n = n; A.S2 = S;
+  A.prio_first = a.depth > 1 ? TSA_PRIO_FIRST : 0;
+  if (const char* pf = getenv("RNA_TSA_PRIO_FIRST")) A.prio_first = atoi(pf);   // developer knob
+  size_t lds_dyn = 4 * nt_bytes;
+  if (const char* pad = getenv("RNA_TSA_LDS_PAD")) lds_dyn += (size_t)atoi(pad);   // developer knob: fewer search workgroups per CU
+  // a search that outgrows its share of pages is searched again when the host sees the count (the caller copies it to
+  // s.retry_flag behind this launch; astar.hip, stage_settled)
+  const bool can_retry = s.retry_flag != nullptr;
+  A.retry_count = can_retry ? tsa_retry_count(e, d) : nullptr;
+  A.retry_list = can_retry ? tsa_retry_list(e, d) : nullptr;
+  A.retry_base = 0;
+  // 16 wavefronts per query where latency counts (one stream, or a batch too small to fill the chip: a lone search
+  // takes 9.1 instead of 12.9 ms), 8 where throughput does (16 in the pipeline: 91.6 k instead of 122.8 k cycles/s)
+  static const bool wide_env = getenv("RNA_TSA_WIDE") != nullptr;   // developer knob: 16 wavefronts per query always
+  const bool wide = wide_env || n <= 32;
+  if (a.depth > 1 && !wide) hipLaunchKernelGGL((tsa_search_kernel<TSA_WAVES, false>), dim3(n), dim3(TSA_WAVES * 64), lds_dyn, st, A);
+  else hipLaunchKernelGGL((tsa_search_kernel<16, false>), dim3(n), dim3(16 * 64), lds_dyn, st, A);
+  RNA_HIP(e, hipGetLastError());
+  memcpy(s.last_launch, &A, sizeof(A));
+  s.last_lds = lds_dyn;
+  s.last_retried = 0;
+  s.retry_armed = can_retry;
   return RNA_OK;
 }
 
@@ -1993,10 +1991,10 @@ int tsa_counters_read(rna_engine* e, unsigned long long* out, bool reset) {
   for (int k = 0; k < TSA_COUNTER_WORDS; ++k) out[k] = 0ull;
   for (int d = 0; d < AstarDevice::MAX_DEPTH; ++d) {
     for (int view = 0; view < 2; ++view) {
-      char* base = static_cast<char*>(view ? a.tsa_aux_retry[d] : a.tsa_aux[d]);
+      char* base = view ? a.stage[d].retry_block : a.stage[d].block;
       if (!base) continue;
       unsigned long long w[TSA_COUNTER_WORDS];
-      char* cnt = base + 256 - sizeof(w);   // (nalloc starts at base + 256 in both views: tsa_stage_view / tsa_retry_view)
+      char* cnt = base + TSA_HEAD_COUNTERS;
       RNA_HIP(e, hipMemcpyAsync(w, cnt, sizeof(w), hipMemcpyDeviceToHost, e->stream));
       if (reset) RNA_HIP(e, hipMemsetAsync(cnt, 0, sizeof(w), e->stream));
       RNA_HIP(e, hipStreamSynchronize(e->stream));
@@ -2035,14 +2033,12 @@ void tsa_stats_dump() {
 #endif
 
 int tsa_settled(rna_engine* e, int slot, const rna_astar_query* q, const rna_astar_result* r, int n, int32_t* d_counts) {
-  const int rows = e->geom.size[0], cols = e->geom.size[1];
-  const int ti = (rows + TI - 1) / TI, tj = (cols + TJ - 1) / TJ;
+  const TsaGrid G = tsa_grid(e);
   const TsaStage S = tsa_stage_view(e, slot);
-  const bool has_retry = e->astar.g_retry[slot] != nullptr;
-  hipLaunchKernelGGL(tsa_settled_kernel, dim3(n), dim3(1024), 0, e->stream, rows, cols, ti, tj, q, r, S,
-                     has_retry ? tsa_retry_view(e, slot, S) : S, has_retry ? tsa_retry_served(e, slot) : nullptr,
-                     has_retry ? tsa_retry_list(e, slot) : nullptr, has_retry ? e->astar.last_retried[slot] : 0,
-                     d_counts, e->geom.start[0], e->geom.start[1]);
+  const AstarStage& s = e->astar.stage[slot];
+  hipLaunchKernelGGL(tsa_settled_kernel, dim3(n), dim3(1024), 0, e->stream, G.rows, G.cols, G.ti, G.tj, q, r, S,
+                     s.retry_pool ? tsa_retry_view(e, slot, S) : S, tsa_retry_served(e, slot), tsa_retry_list(e, slot),
+                     s.retry_pool ? s.last_retried : 0, d_counts, e->geom.start[0], e->geom.start[1]);
   RNA_HIP(e, hipGetLastError());
   return RNA_OK;
 }

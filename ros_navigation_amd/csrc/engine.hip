@@ -707,11 +707,10 @@ int side_join(rna_engine* e) {
     RNA_HIP(e, hipStreamWaitEvent(e->stream, e->ev_vfh_done, 0));
     e->vfh_pending = false;
   }
-  AstarDevice& a = e->astar;
-  for (int d = 0; d < AstarDevice::MAX_DEPTH; ++d)
-    if (a.snap_pending[d]) {
-      RNA_HIP(e, hipStreamWaitEvent(e->stream, a.snap_done[d], 0));
-      a.snap_pending[d] = false;
+  for (AstarStage& s : e->astar.stage)
+    if (s.snap_pending) {
+      RNA_HIP(e, hipStreamWaitEvent(e->stream, s.snap_done, 0));
+      s.snap_pending = false;
     }
   return RNA_OK;
 }
@@ -719,8 +718,8 @@ int side_join(rna_engine* e) {
 int sync_all(rna_engine* e) {
   RNA_HIP(e, hipStreamSynchronize(e->stream));
   if (e->vfh_stream) RNA_HIP(e, hipStreamSynchronize(e->vfh_stream));
-  for (int d = 0; d < AstarDevice::MAX_DEPTH; ++d)
-    if (e->astar.side[d]) RNA_HIP(e, hipStreamSynchronize(e->astar.side[d]));
+  for (const AstarStage& s : e->astar.stage)
+    if (s.stream) RNA_HIP(e, hipStreamSynchronize(s.stream));
   return astar_settle(e);
 }
 

@@ -59,13 +59,38 @@ struct VfhDevice {
   double* ranges_dev = nullptr;
 };
 
+// One pipeline stage of the grid A* (astar.hip owns it; astar_tile.hip lays out its blocks and launches on its stream).
+struct AstarStage {
+  unsigned* pool = nullptr;        // page pool: the pages, then their edge-column copies (astar_tile.hip, TsaStage)
+  int32_t* rev = nullptr;          // reversed-path staging per query
+  char* block = nullptr;           // starts zeroed: ticket and counters | page counts | launch order | mask snapshot | tile -> page | page -> tile
+  unsigned* retry_pool = nullptr;  // only when page_cap < tiles of the map: TSA_RETRY slots with a page per tile, and their block,
+  char* retry_block = nullptr;     // for the second pass over searches that outgrew their pages (astar_tile.hip)
+  hipStream_t stream = nullptr;    // pipelined only (depth > 1); one stream: the engine stream
+  hipEvent_t done = nullptr;       // the search of the stage's last batch (and its second passes so far) has finished
+  hipEvent_t snap_done = nullptr;  // the mask snapshot of the stage's batch (taken on the side stream) has been taken
+  bool snap_pending = false;
+  bool busy = false;               // `done` is recorded and the host has not seen it complete yet
+  unsigned long long seq = 0;      // launch number of the stage's last batch (0: never used)
+  // Searches that outgrew their share of pages are counted by the kernel and the count is copied to pinned host memory behind the search;
+  // their second pass is launched when the host sees it (a launch per batch "in case" cost every stage 0.2 - 4 ms: its workgroups wait for CU slots)
+  int* retry_flag = nullptr;       // the stage's word of AstarDevice::retry_flag (null: the stage has no retry slots)
+  bool retry_armed = false;
+  int last_retried = 0;            // searches of the stage's last batch that went through the second pass
+  size_t last_lds = 0;
+  alignas(8) unsigned char last_launch[384] = {};   // TsaLaunch of the stage's last batch
+};
+// One entry of the launch ring: ticket, launch order and mask snapshot of one batch (AstarDevice::ring_mem + index * ring_stride).
+struct AstarRingEntry {
+  hipEvent_t free = nullptr;       // the search that read this entry last has finished
+  bool used = false;
+};
+
 struct AstarDevice {
   int max_queries = 0;
-  int queue_cap = 0;
   int bucket_width = 128000;        // f-range of one bucket (128 cells; round 6, on the bench: 72 / 96 / 128 / 160 / 200 / 256 k -> 159.8 / 160.8 / 162.2 / 159.7 / 158.5 / 159.3 k cycles/s, profiles/r06_sweep_bucket_width.txt); inside it free wavefronts take the tile with the lowest key (astar_tile.hip)
-  int threads = 512;               // workgroup size of the search kernel (256 / 512 / 1024)
-  // Pipelined batches: `depth` independent sets of search fields + queues, each with its own HIP
-  // stream, so the tail of batch k (few long queries) overlaps the head of batch k+1.
+  // Pipelined batches: `depth` independent stages, each with its own HIP stream, so the tail of batch k (few long
+  // queries) overlaps the head of batch k+1.
 #ifndef RNA_ASTAR_MAX_DEPTH
 #define RNA_ASTAR_MAX_DEPTH 20   // (developer builds may raise it: scripts/r06_depth_hwq.sh)
 #endif
@@ -73,24 +98,11 @@ struct AstarDevice {
   // r06_sweep_depth_hw_queues.txt): the process then holds 25 queues (the stages' streams, the engine stream, the side stream, the null stream).
   static constexpr int MAX_DEPTH = RNA_ASTAR_MAX_DEPTH;
   int depth = 4;
-  int32_t* g[MAX_DEPTH] = {};      // frontier kernel: [max_queries][field_stride] search fields (g << 8) | mask;
-                                   // tile kernel: the stage's page pool (pages, then pending bitmaps), see astar_tile.hip
-  int2* queues[MAX_DEPTH] = {};    // [max_queries][3][queue_cap] (cell, g)
-  int32_t* rev[MAX_DEPTH] = {};    // tile kernel: reversed-path staging per query
+  AstarStage stage[MAX_DEPTH];
+  bool live() const { return stage[0].pool != nullptr; }   // the configuration is allocated
   int rev_cap = 16800;             // g < 2^24 at >= 1000 per step bounds a path to 16 777 cells
-  int mode = 1;                    // 0 = frontier kernel (astar.hip, fallback for maps beyond 65 536 tiles), 1 = tile kernel (default)
-  int page_cap = 0;                // tile kernel: 4 KiB pages per query (0 = one per tile: a search can never run out)
+  int page_cap = 0;                // 4 KiB pages per query (0 = one per tile: a search can never run out)
   int page_cap_request = 0;        // rna_astar_set_page_cap
-  void* tsa_aux[MAX_DEPTH] = {};   // tile kernel: ticket, page counts, launch order, neighbour-mask snapshot, tile -> page tables
-  int32_t* g_retry[MAX_DEPTH] = {};      // tile kernel, only when page_cap < tiles of the map: TSA_RETRY slots with a page per tile,
-  void* tsa_aux_retry[MAX_DEPTH] = {};   // for the second pass over searches that outgrew their pages (astar_tile.hip)
-  hipStream_t side[MAX_DEPTH] = {};
-  hipEvent_t done[MAX_DEPTH] = {}; // search of the batch that last used this set has finished
-  hipEvent_t snap_done[MAX_DEPTH] = {};   // the mask snapshot of the stage's batch (taken on the side stream) has been taken
-  bool snap_pending[MAX_DEPTH] = {};
-  bool busy[MAX_DEPTH] = {};
-  unsigned long long stage_seq[MAX_DEPTH] = {};   // launch number of the stage's last batch (0: never used)
-  hipEvent_t ev_init = nullptr;
   // Pipelined launches: the mask snapshot, the launch order and the ticket of a batch live in an entry of a ring, not in
   // the stage -- they are written on the engine's side stream (CUs the searches cannot take) as soon as the map is
   // composed, before any stage has to be free; the search itself goes to a stage that IS free (the host waits for one).
@@ -98,21 +110,12 @@ struct AstarDevice {
   int ring_n = 0;
   char* ring_mem = nullptr;
   size_t ring_stride = 0;
-  hipEvent_t ring_free[MAX_RING] = {};   // the search that read this entry last has finished
-  bool ring_used[MAX_RING] = {};
+  AstarRingEntry ring[MAX_RING];
+  hipEvent_t ev_init = nullptr;          // the engine stream has reached the launch: the masks are what the batch shall see
   hipEvent_t ev_prep = nullptr;          // snapshot + launch order of the batch being launched are in place
-  // Searches that outgrew their share of pages: counted by the kernel (the count is copied to pinned host memory behind
-  // the search); the second pass over them is
-  // launched when the host sees the count (a launch per batch "in case" cost every stage 0.2 - 4 ms: its workgroups wait
-  // for CU slots like everybody else's)
-  int* retry_flag = nullptr;             // [MAX_DEPTH], pinned host memory: copied from the stage's device counter behind each search
-  bool retry_armed[MAX_DEPTH] = {};
-  int last_retried[MAX_DEPTH] = {};      // searches of the stage's last batch that went through the second pass
-  size_t last_lds[MAX_DEPTH] = {};
-  alignas(8) unsigned char last_launch[MAX_DEPTH][384] = {};   // TsaLaunch of the stage's last batch
+  int* retry_flag = nullptr;             // pinned host memory, an int per possible stage: copied from the stage's device counter behind each search
   unsigned long long launches = 0;
   int last_slot = 0;
-  size_t field_stride = 0;         // words per query field incl. padding
   rna_astar_query* queries_dev = nullptr;
   rna_astar_result* results_dev = nullptr;
   int32_t* paths_dev = nullptr;
@@ -329,19 +332,25 @@ int frontiers_release(rna_engine* e);
 int sync_all(rna_engine* e);          // main stream + every A* side stream
 // tile-synchronous A* (astar_tile.hip)
 bool tsa_supported(const rna_engine* e);
-int tsa_tiles(const rna_engine* e);                                   // 32 x 32 tiles of the map
-size_t tsa_pool_bytes(int max_queries, int cap);                      // pages + pending bitmaps of one pipeline stage
-size_t tsa_aux_bytes(const rna_engine* e, int max_queries, int cap);  // per stage, must start zeroed
-int tsa_stage_prepare(rna_engine* e, int slot);                       // fresh stage: page 0 of every slot "unreached"
+int tsa_tiles(const rna_engine* e);                                   // 64 x 16 tiles of the map
 constexpr int TSA_RETRY = 8;                                          // full-size retry slots per stage
+// sizes at e->astar's max_queries and page_cap: a stage's page pool and its block (must start zeroed), the same of its retry slots, a ring entry
+size_t tsa_pool_bytes(int max_queries, int cap);
+size_t tsa_stage_bytes(const rna_engine* e);
 size_t tsa_retry_pool_bytes(const rna_engine* e);
-size_t tsa_retry_aux_bytes(const rna_engine* e);
-int tsa_retry_prepare(rna_engine* e, int slot);
-size_t tsa_ring_bytes(const rna_engine* e, int max_queries);            // one entry of the launch ring
-int tsa_retry_launch(rna_engine* e, int slot, hipStream_t search_stream, int count);   // second pass over `count` listed searches
-int tsa_launch(rna_engine* e, int slot, hipStream_t init_stream, hipStream_t search_stream, hipEvent_t ev_init,
-               const rna_astar_query* q_dev, int n, int32_t* paths_dev, int max_len, rna_astar_result* res_dev);
-int tsa_settled(rna_engine* e, int slot, const rna_astar_query* q, const rna_astar_result* r, int n, int32_t* d_counts);
+size_t tsa_retry_bytes(const rna_engine* e);
+size_t tsa_ring_bytes(const rna_engine* e);
+int tsa_stage_prepare(rna_engine* e, int d);                          // fresh stage: page 0 of every slot "unreached"
+int tsa_retry_prepare(rna_engine* e, int d);
+// A batch on stage d, three launches on the streams the caller hands in (astar.hip orders them with its events): the mask
+// snapshot and the launch order go into ring entry `ring`, or into the stage's own block if ring < 0; the search reads them there.
+int tsa_snapshot(rna_engine* e, int d, int ring, hipStream_t st);
+int tsa_order(rna_engine* e, int d, int ring, hipStream_t st, const rna_astar_query* q_dev, int n);
+int tsa_search(rna_engine* e, int d, int ring, hipStream_t st, const rna_astar_query* q_dev, int n, int32_t* paths_dev, int max_len,
+               rna_astar_result* res_dev);
+int* tsa_retry_count(const rna_engine* e, int d);   // device int: searches of the stage's batch that ended with status 5
+int tsa_retry_launch(rna_engine* e, int d, hipStream_t st, int count);   // second pass over `count` listed searches
+int tsa_settled(rna_engine* e, int d, const rna_astar_query* q, const rna_astar_result* r, int n, int32_t* d_counts);
 int tsa_counters_read(rna_engine* e, unsigned long long* out, bool reset);   // sums the job counters of every stage view into out[16]
 
 }  // namespace rna

@@ -209,13 +209,13 @@ int shortcut_paths(rna_engine* e, const int32_t* paths, const rna_astar_result* 
   if (!host) {
     // device pointers may be the outputs of rna_astar_batch_device batches still in flight on the pipeline stages' own
     // streams: the engine stream waits for every busy stage's search (a wait on an event that is complete costs nothing).
-    // Skipping a stage that is not busy is no race: busy[d] is host state, set when done[d] is recorded behind a search and
+    // Skipping a stage that is not busy is no race: `busy` is host state, set when `done` is recorded behind a search and
     // cleared only after the host has seen that event complete (an event query or a synchronisation, then stage_settled in
     // astar.hip), so a stage that is not busy has nothing in flight.
     const AstarDevice& a = e->astar;
     if (a.depth > 1)
       for (int d = 0; d < a.depth && d < AstarDevice::MAX_DEPTH; ++d)
-        if (a.busy[d] && a.done[d]) RNA_HIP(e, hipStreamWaitEvent(e->stream, a.done[d], 0));
+        if (a.stage[d].busy && a.stage[d].done) RNA_HIP(e, hipStreamWaitEvent(e->stream, a.stage[d].done, 0));
   }
   const int32_t* d_paths = paths;
   const rna_astar_result* d_res = results;

@@ -21,7 +21,7 @@ import pytest
 from ros_navigation_amd import synth
 
 import _oracle as O
-from _gpu import R, make_engine_and_geom, to_buffer, to_map  # noqa: F401  (R: the fixture)
+from _gpu import Hip, R, make_engine_and_geom, to_buffer, to_map  # noqa: F401  (R: the fixture)
 from test_gpu_parity import check_astar
 
 pytestmark = pytest.mark.gpu
@@ -315,4 +315,42 @@ def test_retry_slots_are_reused_as_they_were_left(R, name, depth):
         for _ in range(depth):
             check_on_map(e, g, master, q)
             assert e.astar_effective_config()[1] == 3
+    e.close()
+
+
+# ---- case 6: more device batches in flight than the launch ring has entries ----
+@pytest.mark.parametrize("page_cap", [0, 3])
+@pytest.mark.parametrize("name", sorted(MAPS))
+def test_device_batches_beyond_the_launch_ring(R, name, page_cap):
+    """ten batches through rna_astar_batch_device at depth 2 (a ring of four entries), nothing waited for in between: from the
+    fifth launch on the host has to settle an older stage -- with three pages per query, send out its second pass too -- before
+    the launch may write the ring entry that stage's batch read"""
+    rows, cols, _, _ = the_map(name)
+    batches = [corner_queries(name, 8, SEED_A[name]), corner_queries(name, 8, SEED_A[name], reverse=True)]
+    fields = [oracle_fields(name, q) for q in batches]
+    for f in fields:
+        assert all(r.status == 0 for r, _, _ in f)
+        assert page_cap == 0 or sum(r.settled > page_cap * 1024 for r, _, _ in f) >= 4     # a second pass is due after every launch
+    e, _ = engine_for(R, name, 2, max_queries=8, bucket_width=2828)
+    if page_cap:
+        e.astar_page_cap(page_cap)
+    hip, max_len = Hip(), rows * cols
+    d_q = [hip.upload(q) for q in batches]
+    outs = []
+    for b in range(10):
+        d_paths, d_res = hip.alloc(8 * max_len * 4), hip.alloc(8 * R.capi.ASTAR_RESULT_DTYPE.itemsize)
+        e.astar_device(d_q[b % 2], 8, d_paths, max_len, d_res)
+        outs.append((d_paths, d_res))
+    e.synchronize()
+    if page_cap:
+        assert e.astar_effective_config()[1] == page_cap
+    for b, (d_paths, d_res) in enumerate(outs):
+        res = hip.download(d_res, np.uint8, 8 * R.capi.ASTAR_RESULT_DTYPE.itemsize).view(R.capi.ASTAR_RESULT_DTYPE)
+        paths = hip.download(d_paths, np.int32, 8 * max_len).reshape(8, max_len)
+        assert 5 not in res["status"].tolist(), (b, res["status"])
+        for k, (ores, opath, _) in enumerate(fields[b % 2]):
+            assert (res["status"][k], res["cost"][k], res["path_len"][k]) == (ores.status, ores.cost, ores.path_len), (b, k, res[k])
+            assert np.array_equal(paths[k, :ores.path_len], opath), (b, k)
+    for p in d_q + [p for o in outs for p in o]:
+        hip.free(p)
     e.close()
