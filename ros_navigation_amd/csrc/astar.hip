@@ -188,7 +188,6 @@ int ensure_config(rna_engine* e) {
   for (;;) {
     const int rc = alloc_stages(e);
     if (rc != RNA_ENOMEM) return rc;
-    (void)hipGetLastError();   // the failed hipMalloc must not surface at the next launch check
     if (a.page_cap > 64 && a.page_cap > ntile / 2) a.page_cap = (ntile + 1) / 2;
     else if (a.depth > 1) a.depth = a.depth > 2 ? a.depth * 3 / 4 : 1;
     else if (a.page_cap > 64 && a.page_cap > ntile / 8) a.page_cap /= 2;
@@ -523,16 +522,11 @@ extern "C" int rna_astar_settled_counts(rna_engine* e, int32_t* counts_host, int
   AstarDevice& a = e->astar;
   if (!a.live() || !a.last_queries || n != a.last_n) return fail(e, RNA_ESTATE, "no resident A* batch of that size");
   RNA_ENTER(e);
-  int32_t* d_counts = nullptr;
   int rc = sync_all(e);
   if (rc != RNA_OK) return rc;
-  if ((rc = dev_alloc(e, &d_counts, (size_t)n)) != RNA_OK) return rc;
+  Staging st(e, "rna_astar_settled_counts");
+  int32_t* d_counts = st.out(counts_host, (size_t)n);
+  if (!st.ok()) return st.finish();
   rc = tsa_settled(e, a.last_slot, a.last_queries, a.last_results, n, d_counts);
-  if (rc != RNA_OK) { dev_free(&d_counts); return rc; }
-  hipError_t st = hipGetLastError();
-  if (st == hipSuccess) st = hipMemcpyAsync(counts_host, d_counts, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  dev_free(&d_counts);
-  if (st != hipSuccess) return fail(e, RNA_EHIP, hipGetErrorString(st));
-  return RNA_OK;
+  return rc != RNA_OK ? rc : st.finish();
 }

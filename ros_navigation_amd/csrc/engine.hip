@@ -388,21 +388,13 @@ static int get_submap(rna_engine* e, int layer, double px, double py, double lx,
   const size_t n = (size_t)si.size[0] * si.size[1];
   if (n > cap) return rna::fail(e, RNA_ECAPACITY, "rna_get_submap: output buffer smaller than the submap");
   RNA_ENTER(e);
-  float* dst = out;
-  float* staging = nullptr;
-  if (to_host) {
-    RNA_HIP(e, hipMalloc(&staging, n * sizeof(float)));
-    dst = staging;
-  }
-  hipLaunchKernelGGL(submap_gather_kernel, dim3(grid_for(n, 256)), dim3(256), 0, e->stream, e->layer[layer],
-                     e->geom.size[0], e->geom.size[1], si.top_left[0], si.top_left[1], si.size[0], si.size[1], dst);
-  hipError_t err = hipGetLastError();
-  if (err == hipSuccess && to_host)
-    err = hipMemcpyAsync(out, staging, n * sizeof(float), hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess && to_host) err = hipStreamSynchronize(e->stream);
-  if (staging) (void)hipFree(staging);
-  RNA_HIP(e, err);
-  return 1;
+  Staging st(e, "rna_get_submap");
+  float* dst = to_host ? st.out(out, n) : out;
+  if (st.ok())
+    hipLaunchKernelGGL(submap_gather_kernel, dim3(grid_for(n, 256)), dim3(256), 0, e->stream, e->layer[layer],
+                       e->geom.size[0], e->geom.size[1], si.top_left[0], si.top_left[1], si.size[0], si.size[1], dst);
+  const int rc = st.finish();
+  return rc == RNA_OK ? 1 : rc;
 }
 
 extern "C" int rna_last_dirty_tiles(rna_engine* e, uint8_t* flags_host, size_t n_tiles) {

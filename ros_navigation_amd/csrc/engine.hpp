@@ -11,6 +11,12 @@
 #include "../../include/rna.h"
 #include "gridmath.hpp"
 
+// control words of the goal field and of the frontiers: each private to its file (defined in its unnamed namespace)
+namespace {
+struct GfCtl;
+struct FrCtl;
+}  // namespace
+
 namespace rna {
 
 constexpr int TILE = 64;  // dirty-tracking / mask tile edge (cells)
@@ -138,14 +144,23 @@ struct FootprintPlan {
   int w[64] = {};
 };
 
+// A module's device control words and their pinned host copy.
+template <typename T>
+struct CtlPair {
+  T* dev = nullptr;
+  T* host = nullptr;
+  int alloc(rna_engine* e);     // RNA_ENOMEM when either is refused
+  void release();
+  int read(rna_engine* e);      // the launch check of the kernels enqueued so far, then the words as they leave them: returns with the engine stream idle
+};
+
 // The goal distance field (goal_field.hip): a snapshot of cost-to-goal and canonical steps, built on request.
 struct GoalField {
   int32_t* field = nullptr;        // [ncell] buffer order: exact distance, RNA_GOAL_FIELD_UNREACHED / _FAR
   uint8_t* next = nullptr;         // [ncell] neighbour number 0-7 of the canonical step, 8 = goal, 254 = far, 255 = unreached
   int* keys = nullptr;             // [2][tiles]: pending key per map-space tile, this round's and the next one's
   uint8_t* touched = nullptr;      // [tiles]: the tile has been relaxed during this build
-  void* ctl = nullptr;             // device control words (GfCtl)
-  void* ctl_host = nullptr;        // their pinned copy
+  CtlPair<GfCtl> ctl;              // control words
   int rows = 0, cols = 0, s0 = 0, s1 = 0;   // geometry the field was built with (paths are walked in its map space)
   unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
   rna_goal_field_info info{-1, 0, 0, 0, 0, 0, 0, 0};
@@ -175,8 +190,7 @@ struct Frontiers {
   rna_frontier* rec = nullptr;     // [rec_cap] one accumulator per cluster, in arrival order
   rna_frontier* out = nullptr;     // [rec_cap] the records that passed the size filter
   int rec_cap = 0;
-  void* ctl = nullptr;             // device control words (FrCtl)
-  void* ctl_host = nullptr;        // their pinned copy
+  CtlPair<FrCtl> ctl;              // control words
   bool built = false;
   unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
   rna_frontier_info info{0, 0, 0, 0, 0, 0, 0, 0};
@@ -285,18 +299,118 @@ struct KernelTimer {
   }
 };
 
+// A refused hipMalloc is RNA_ENOMEM, and its HIP error is consumed: left behind, it would be what the thread's next launch
+// check (hipGetLastError) reports.
 template <typename T>
 inline int dev_alloc(rna_engine* e, T** p, size_t n) {
   if (*p) { (void)hipFree(*p); *p = nullptr; }
   if (n == 0) return RNA_OK;
   hipError_t st = hipMalloc((void**)p, n * sizeof(T));
-  if (st != hipSuccess) { *p = nullptr; return fail(e, RNA_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(st)); }
+  if (st != hipSuccess) {
+    *p = nullptr;
+    (void)hipGetLastError();
+    return fail(e, RNA_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(st));
+  }
   return RNA_OK;
 }
 
 template <typename T>
 inline void dev_free(T** p) {
   if (*p) { (void)hipFree(*p); *p = nullptr; }
+}
+
+// The device temporaries of ONE C-ABI call (`who`, for the messages) that takes host pointers, on the engine stream: in()
+// uploads, out() registers a download, scratch() only allocates; the caller launches on e->stream and returns finish().
+// The first failure latches: later in / out / scratch calls enqueue nothing and return nullptr, and finish() reports it
+// -- RNA_ENOMEM for a refused allocation (as dev_alloc, its HIP error consumed), RNA_EHIP for anything else -- with e->err
+// set.  Plain hipMalloc / hipFree per call, freed by the destructor once the stream has drained (kernels and copies in
+// flight read and write the buffers).
+class Staging {
+ public:
+  Staging(rna_engine* e, const char* who) : e_(e), who_(who) {}
+  Staging(const Staging&) = delete;
+  Staging& operator=(const Staging&) = delete;
+  ~Staging() {
+    if (!bufs_.empty() && !drained_) (void)hipStreamSynchronize(e_->stream);
+    for (void* p : bufs_) (void)hipFree(p);
+  }
+  bool ok() const { return rc_ == RNA_OK; }
+  // n == 0 still yields a valid pointer (the kernels' device forms reject NULL)
+  template <typename T>
+  T* scratch(size_t n) {
+    if (!ok()) return nullptr;
+    void* p = nullptr;
+    if (!hip(hipMalloc(&p, (n ? n : 1) * sizeof(T)), "hipMalloc", RNA_ENOMEM)) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    bufs_.push_back(p);
+    return static_cast<T*>(p);
+  }
+  template <typename T>
+  T* in(const T* host, size_t n) {
+    T* d = scratch<T>(n);
+    // (pageable host memory: the copy has left the caller's array when the call returns)
+    if (d && n) hip(hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, e_->stream), "upload");
+    return ok() ? d : nullptr;
+  }
+  // finish() copies the n elements to host; zero: the buffer is cleared on the stream first
+  template <typename T>
+  T* out(T* host, size_t n, bool zero = false) {
+    T* d = scratch<T>(n);
+    if (d && n && zero) hip(hipMemsetAsync(d, 0, n * sizeof(T), e_->stream), "clear");
+    if (!ok()) return nullptr;
+    if (n) downloads_.push_back(Download{host, d, n * sizeof(T)});
+    return d;
+  }
+  // The launch check, the registered downloads, the stream synchronisation.  A call that staged nothing (the _device form
+  // of an entry point that has both) stops after the launch check: it has no temporaries to outlive.
+  int finish() {
+    if (ok()) hip(hipGetLastError(), "launch");
+    if (bufs_.empty()) return rc_;
+    for (const Download& d : downloads_)
+      if (ok()) hip(hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, e_->stream), "download");
+    if (ok()) {
+      hip(hipStreamSynchronize(e_->stream), "synchronize");
+      drained_ = ok();
+    }
+    return rc_;
+  }
+
+ private:
+  struct Download { void* host; const void* dev; size_t bytes; };
+  bool hip(hipError_t st, const char* what, int code = RNA_EHIP) {
+    if (st != hipSuccess && ok()) rc_ = fail(e_, code, std::string(who_) + ": " + what + ": " + hipGetErrorString(st));
+    return st == hipSuccess;
+  }
+  rna_engine* e_;
+  const char* who_;
+  int rc_ = RNA_OK;
+  bool drained_ = false;
+  std::vector<void*> bufs_;
+  std::vector<Download> downloads_;
+};
+
+template <typename T>
+int CtlPair<T>::alloc(rna_engine* e) {
+  const int rc = dev_alloc(e, &dev, 1);
+  if (rc != RNA_OK) return rc;
+  if (hipHostMalloc((void**)&host, sizeof(T)) == hipSuccess) return RNA_OK;
+  host = nullptr;
+  (void)hipGetLastError();
+  return fail(e, RNA_ENOMEM, "hipHostMalloc failed");
+}
+template <typename T>
+void CtlPair<T>::release() {
+  dev_free(&dev);
+  if (host) { (void)hipHostFree(host); host = nullptr; }
+}
+template <typename T>
+int CtlPair<T>::read(rna_engine* e) {
+  RNA_HIP(e, hipGetLastError());
+  RNA_HIP(e, hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, e->stream));
+  RNA_HIP(e, hipStreamSynchronize(e->stream));
+  return RNA_OK;
 }
 
 // the engine stream waits for the side work in flight (see rna_engine::vfh_stream); cheap when there is none

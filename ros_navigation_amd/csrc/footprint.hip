@@ -282,18 +282,14 @@ extern "C" int rna_astar_download_blocked(rna_engine* e, uint8_t* host, size_t n
   RNA_ENTER(e);
   int rc = map_prepare_nbr(e);
   if (rc != RNA_OK) return rc;
-  uint8_t* staging = nullptr;
-  RNA_HIP(e, hipMalloc(&staging, n));
+  Staging st(e, "rna_astar_download_blocked");
+  uint8_t* staging = st.out(host, n);
   const size_t blocks = std::min<size_t>((n + 255) / 256, 8192);
-  hipLaunchKernelGGL(blocked_bytes_kernel, dim3((unsigned)blocks), dim3(256), 0, e->stream, staging,
-                     e->robot_r > 0.0 ? e->fp_bits : (const unsigned long long*)nullptr, e->layer[RNA_LAYER_MASTER], e->geom.size[0],
-                     e->geom.size[1], e->tiles_i, e->geom.start[0], e->geom.start[1]);
-  hipError_t err = hipGetLastError();
-  if (err == hipSuccess) err = hipMemcpyAsync(host, staging, n, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(staging);
-  RNA_HIP(e, err);
-  return RNA_OK;
+  if (st.ok())
+    hipLaunchKernelGGL(blocked_bytes_kernel, dim3((unsigned)blocks), dim3(256), 0, e->stream, staging,
+                       e->robot_r > 0.0 ? e->fp_bits : (const unsigned long long*)nullptr, e->layer[RNA_LAYER_MASTER], e->geom.size[0],
+                       e->geom.size[1], e->tiles_i, e->geom.start[0], e->geom.start[1]);
+  return st.finish();
 }
 
 static int if_blocked(rna_engine* e, const double* xy, int n, double radius, uint8_t* out, bool host) {
@@ -301,27 +297,13 @@ static int if_blocked(rna_engine* e, const double* xy, int n, double radius, uin
   if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(e, RNA_EINVAL, "radius must be finite and >= 0");
   if (n == 0) return RNA_OK;
   RNA_ENTER(e);
-  double* d_xy = const_cast<double*>(xy);
-  uint8_t* d_out = out;
-  if (host) {
-    RNA_HIP(e, hipMalloc(&d_xy, (size_t)n * 2 * sizeof(double)));
-    if (hipMalloc(&d_out, (size_t)n) != hipSuccess) { (void)hipFree(d_xy); return fail(e, RNA_ENOMEM, "hipMalloc failed"); }
-  }
-  hipError_t err = hipSuccess;
-  if (host) err = hipMemcpyAsync(d_xy, xy, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, e->stream);
-  if (err == hipSuccess) {
+  Staging st(e, "rna_if_blocked_batch");
+  const double* d_xy = host ? st.in(xy, (size_t)n * 2) : xy;
+  uint8_t* d_out = host ? st.out(out, (size_t)n) : out;
+  if (st.ok())
     hipLaunchKernelGGL(if_blocked_kernel, dim3((n + 127) / 128), dim3(128), 0, e->stream, d_xy, n, radius, e->geom,
                        e->layer[RNA_LAYER_MASTER], d_out);
-    err = hipGetLastError();
-  }
-  if (host) {
-    if (err == hipSuccess) err = hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    (void)hipFree(d_xy);
-    (void)hipFree(d_out);
-  }
-  RNA_HIP(e, err);
-  return RNA_OK;
+  return st.finish();
 }
 
 extern "C" int rna_if_blocked_batch(rna_engine* e, const double* xy_host, int n, double radius, uint8_t* out_host) {

@@ -347,8 +347,7 @@ int frontiers_release(rna_engine* e) {
   dev_free(&f.rec);
   dev_free(&f.out);
   f.rec_cap = 0;
-  if (f.ctl) { (void)hipFree(f.ctl); f.ctl = nullptr; }
-  if (f.ctl_host) { (void)hipHostFree(f.ctl_host); f.ctl_host = nullptr; }
+  f.ctl.release();
   f.built = false;
   f.info = rna_frontier_info{0, 0, 0, 0, 0, 0, 0, 0};
   return RNA_OK;
@@ -363,8 +362,7 @@ int fr_alloc(rna_engine* e) {
   if (f.labels) return RNA_OK;
   int rc = dev_alloc(e, &f.labels, e->ncell);
   if (rc == RNA_OK) rc = dev_alloc(e, &f.slot, e->ncell);
-  if (rc == RNA_OK && hipMalloc(&f.ctl, sizeof(FrCtl)) != hipSuccess) rc = fail(e, RNA_ENOMEM, "hipMalloc failed");
-  if (rc == RNA_OK && hipHostMalloc(&f.ctl_host, sizeof(FrCtl)) != hipSuccess) rc = fail(e, RNA_ENOMEM, "hipHostMalloc failed");
+  if (rc == RNA_OK) rc = f.ctl.alloc(e);
   if (rc != RNA_OK) {
     const std::string msg = e->err;
     frontiers_release(e);
@@ -392,8 +390,8 @@ extern "C" int rna_frontiers_build(rna_engine* e, int min_size, unsigned flags, 
   f.info = rna_frontier_info{0, 0, 0, 0, 0, 0, 0, 0};
   const Geom& g = e->geom;
   const int rows = g.size[0], cols = g.size[1], s0 = g.start[0], s1 = g.start[1], ncell = (int)e->ncell;
-  FrCtl* ctl = static_cast<FrCtl*>(f.ctl);
-  FrCtl* host = static_cast<FrCtl*>(f.ctl_host);
+  FrCtl* const ctl = f.ctl.dev;
+  const FrCtl* const host = f.ctl.host;
   const dim3 tiles(e->tiles_i, e->tiles_j);
   const unsigned cell_blocks = (unsigned)std::min<size_t>((e->ncell + 255) / 256, 8192);
   RNA_HIP(e, hipMemsetAsync(ctl, 0, sizeof(FrCtl), e->stream));
@@ -401,9 +399,7 @@ extern "C" int rna_frontiers_build(rna_engine* e, int min_size, unsigned flags, 
                      e->layer[RNA_LAYER_MASTER], ctl, rows, cols, s0, s1);
   hipLaunchKernelGGL(fr_seam_kernel, tiles, dim3(256), 0, e->stream, f.labels, ctl, rows, cols, s0, s1, ncell);
   hipLaunchKernelGGL(fr_flatten_kernel, dim3(cell_blocks), dim3(256), 0, e->stream, f.labels, f.slot, ctl, ncell);
-  RNA_HIP(e, hipGetLastError());
-  RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(FrCtl), hipMemcpyDeviceToHost, e->stream));
-  RNA_HIP(e, hipStreamSynchronize(e->stream));
+  if ((rc = f.ctl.read(e)) != RNA_OK) return rc;
   if (host->overflow) return fail(e, RNA_ECAPACITY, "rna_frontiers_build: a union-find loop exceeded its bound");
   const int roots = host->roots;
   if (roots > f.rec_cap) {   // (no kernel in flight reads the records: a build returns when it is complete)
@@ -419,9 +415,7 @@ extern "C" int rna_frontiers_build(rna_engine* e, int min_size, unsigned flags, 
     hipLaunchKernelGGL(fr_stats_kernel, dim3(cell_blocks), dim3(256), 0, e->stream, f.labels, f.slot, f.rec, roots,
                        rank ? e->gfield.field : (const int32_t*)nullptr, ctl, rows, cols, s0, s1, ncell);
     hipLaunchKernelGGL(fr_compact_kernel, dim3(rec_blocks), dim3(256), 0, e->stream, f.rec, roots, min_size, rank ? 1 : 0, f.out, ctl);
-    RNA_HIP(e, hipGetLastError());
-    RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(FrCtl), hipMemcpyDeviceToHost, e->stream));
-    RNA_HIP(e, hipStreamSynchronize(e->stream));
+    if ((rc = f.ctl.read(e)) != RNA_OK) return rc;
     if (host->overflow) return fail(e, RNA_ECAPACITY, "rna_frontiers_build: a cluster root without a record");
   }
   f.info = rna_frontier_info{host->cells, roots, host->kept, host->largest, min_size, rank ? 1 : 0, 0, 0};

@@ -551,8 +551,7 @@ int goal_field_release(rna_engine* e) {
   dev_free(&f.owner);
   f.sources = rna_goal_field_sources_info{0, 0, 0, 0, 0, {0, 0, 0}};
   f.pen_current = false;
-  if (f.ctl) { (void)hipFree(f.ctl); f.ctl = nullptr; }
-  if (f.ctl_host) { (void)hipHostFree(f.ctl_host); f.ctl_host = nullptr; }
+  f.ctl.release();
   f.info = rna_goal_field_info{-1, 0, 0, 0, 0, 0, 0, 0};
   return RNA_OK;
 }
@@ -569,8 +568,7 @@ int gf_alloc(rna_engine* e) {
   if (rc == RNA_OK) rc = dev_alloc(e, &f.next, e->ncell);
   if (rc == RNA_OK) rc = dev_alloc(e, &f.keys, 2 * ntile);
   if (rc == RNA_OK) rc = dev_alloc(e, &f.touched, ntile);
-  if (rc == RNA_OK && hipMalloc(&f.ctl, sizeof(GfCtl)) != hipSuccess) rc = fail(e, RNA_ENOMEM, "hipMalloc failed");
-  if (rc == RNA_OK && hipHostMalloc(&f.ctl_host, sizeof(GfCtl)) != hipSuccess) rc = fail(e, RNA_ENOMEM, "hipHostMalloc failed");
+  if (rc == RNA_OK) rc = f.ctl.alloc(e);
   if (rc != RNA_OK) {
     const std::string msg = e->err;
     goal_field_release(e);
@@ -600,9 +598,10 @@ int gf_log2_ceil(size_t n) {
 // The owner pass of a finalized field (see the head of the file), on the engine stream; returns when the labels are complete.
 int gf_owners(rna_engine* e, int* rounds_out) {
   GoalField& f = e->gfield;
-  GfCtl* ctl = static_cast<GfCtl*>(f.ctl);
-  GfCtl* host = static_cast<GfCtl*>(f.ctl_host);
+  GfCtl* const ctl = f.ctl.dev;
+  const GfCtl* const host = f.ctl.host;
   const dim3 grid(e->tiles_i, e->tiles_j), block(256);
+  int rc;
   hipLaunchKernelGGL(gf_owner_tile_kernel, grid, block, 0, e->stream, f.next, f.owner, f.touched, f.rows, f.cols, f.s0, f.s1);
   // border rounds in chunks until one leaves nothing unresolved: at most ceil(log2 cells) of them (gf_owner_jump_kernel)
   const int cap = std::max(1, gf_log2_ceil(e->ncell));
@@ -610,9 +609,7 @@ int gf_owners(rna_engine* e, int* rounds_out) {
   while (clean < 0) {
     for (int k = 0; k < GF_OWNER_CHUNK && round < cap; ++k, ++round)
       hipLaunchKernelGGL(gf_owner_jump_kernel<false>, grid, block, 0, e->stream, f.owner, f.touched, ctl, round, f.rows, f.cols, f.s0, f.s1);
-    RNA_HIP(e, hipGetLastError());
-    RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
-    RNA_HIP(e, hipStreamSynchronize(e->stream));
+    if ((rc = f.ctl.read(e)) != RNA_OK) return rc;
     for (int r = 0; r < round && clean < 0; ++r)
       if (host->own_unres[r] == 0) clean = r;
     if (clean < 0 && round >= cap)
@@ -622,9 +619,7 @@ int gf_owners(rna_engine* e, int* rounds_out) {
   // the gather: every cell, its count goes into the slot behind the border rounds
   const int slot = GF_OWNER_SLOTS - 1;
   hipLaunchKernelGGL(gf_owner_jump_kernel<true>, grid, block, 0, e->stream, f.owner, f.touched, ctl, slot, f.rows, f.cols, f.s0, f.s1);
-  RNA_HIP(e, hipGetLastError());
-  RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
-  RNA_HIP(e, hipStreamSynchronize(e->stream));
+  if ((rc = f.ctl.read(e)) != RNA_OK) return rc;
   if (host->own_unres[slot] != 0)
     return fail(e, RNA_ECAPACITY, "rna_goal_field_build_multi: the owner pass left " + std::to_string(host->own_unres[slot]) +
                                       " cells unresolved");
@@ -665,8 +660,8 @@ int gf_build(rna_engine* e, const int32_t* goals, const int32_t* seed, int n, in
   // refresh, the table upload -- leaves the previous field in place: its buffers have not been touched yet)
   f.info.goal = -1;
   f.sources = rna_goal_field_sources_info{0, 0, 0, 0, 0, {0, 0, 0}};
-  GfCtl* ctl = static_cast<GfCtl*>(f.ctl);
-  GfCtl* host = static_cast<GfCtl*>(f.ctl_host);
+  GfCtl* const ctl = f.ctl.dev;
+  const GfCtl* const host = f.ctl.host;
   const float* master = e->layer[RNA_LAYER_MASTER];
   const unsigned long long* bits = e->robot_r > 0.0 ? e->fp_bits : (const unsigned long long*)nullptr;
   const dim3 per_source((unsigned)((n + 255) / 256));
@@ -690,9 +685,7 @@ int gf_build(rna_engine* e, const int32_t* goals, const int32_t* seed, int n, in
       hipLaunchKernelGGL(pen ? gf_round_kernel<true> : gf_round_kernel<false>, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream,
                          f.field, e->nbr, f.keys, f.touched, ctl, (int)(round % 6), width, rows, cols, s0, s1,
                          pen ? e->clearance.clr : (const uint16_t*)nullptr, f.pen, pen_r2);
-    RNA_HIP(e, hipGetLastError());
-    RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
-    RNA_HIP(e, hipStreamSynchronize(e->stream));
+    if ((rc = f.ctl.read(e)) != RNA_OK) return rc;
     // (the device form's sources are seen here first: the seed kernel skipped the bad ones, the field is dropped)
     if (host->invalid_sources)
       return fail(e, RNA_EINVAL, std::string(who) + ": " + std::to_string(host->invalid_sources) +
@@ -708,9 +701,7 @@ int gf_build(rna_engine* e, const int32_t* goals, const int32_t* seed, int n, in
   hipLaunchKernelGGL(pen ? gf_finalize_kernel<true> : gf_finalize_kernel<false>, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream,
                      f.field, e->nbr, f.next, f.touched, ctl, rows, cols, s0, s1, pen ? e->clearance.clr : (const uint16_t*)nullptr,
                      f.pen, pen_r2);
-  RNA_HIP(e, hipGetLastError());
-  RNA_HIP(e, hipMemcpyAsync(host, ctl, sizeof(GfCtl), hipMemcpyDeviceToHost, e->stream));
-  RNA_HIP(e, hipStreamSynchronize(e->stream));
+  if ((rc = f.ctl.read(e)) != RNA_OK) return rc;
   f.rows = rows; f.cols = cols; f.s0 = s0; f.s1 = s1;
   f.epoch = e->map_epoch;
   f.cost_changed = false;
@@ -764,18 +755,13 @@ extern "C" int rna_goal_field_build_multi(rna_engine* e, const int32_t* goals_ho
       return fail(e, RNA_EINVAL, "rna_goal_field_build_multi: start cost outside [0, 2^30)");
   }
   RNA_ENTER(e);
-  int32_t *d_goals = nullptr, *d_seed = nullptr;
-  hipError_t err = hipMalloc(&d_goals, (size_t)n * sizeof(int32_t));
-  if (err == hipSuccess && seed_host) err = hipMalloc(&d_seed, (size_t)n * sizeof(int32_t));
-  if (err == hipSuccess) err = hipMemcpyAsync(d_goals, goals_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-  if (err == hipSuccess && seed_host) err = hipMemcpyAsync(d_seed, seed_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-  // (pageable host memory: the copies have left the caller's arrays when the calls return; the build ends with the stream idle)
-  const int rc = err == hipSuccess ? gf_build(e, d_goals, d_seed, n, -1, flags, info_host, "rna_goal_field_build_multi") : RNA_OK;
-  if (rc != RNA_OK) (void)hipStreamSynchronize(e->stream);   // a failed build may have left kernels behind that read the arrays
-  if (d_goals) (void)hipFree(d_goals);
-  if (d_seed) (void)hipFree(d_seed);
-  RNA_HIP(e, err);
-  return rc;
+  Staging st(e, "rna_goal_field_build_multi");
+  const int32_t* d_goals = st.in(goals_host, (size_t)n);
+  const int32_t* d_seed = seed_host ? st.in(seed_host, (size_t)n) : nullptr;
+  if (!st.ok()) return st.finish();
+  // (a failed build may have left kernels behind that read the arrays: st waits for the stream before it frees them)
+  const int rc = gf_build(e, d_goals, d_seed, n, -1, flags, info_host, "rna_goal_field_build_multi");
+  return rc != RNA_OK ? rc : st.finish();
 }
 
 extern "C" int rna_goal_field_sources_info_get(const rna_engine* e, rna_goal_field_sources_info* out) {
@@ -858,35 +844,15 @@ static int gf_paths(rna_engine* e, const int32_t* starts, int n, int32_t* paths,
   if (f.info.goal < 0) return fail(e, RNA_ESTATE, "rna_goal_field_paths: no field has been built");
   if (n == 0) return RNA_OK;
   RNA_ENTER_NOJOIN(e);
-  int32_t *d_starts = const_cast<int32_t*>(starts), *d_paths = paths;
-  rna_astar_result* d_res = results;
-  hipError_t err = hipSuccess;
-  if (host) {
-    d_starts = d_paths = nullptr;
-    d_res = nullptr;
-    err = hipMalloc(&d_starts, (size_t)n * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc(&d_paths, (size_t)n * max_path_len * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc(&d_res, (size_t)n * sizeof(rna_astar_result));
-    if (err == hipSuccess) err = hipMemcpyAsync(d_starts, starts, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    // (cells behind a path's end come back as 0; the _device form leaves them as the caller's buffer had them)
-    if (err == hipSuccess) err = hipMemsetAsync(d_paths, 0, (size_t)n * max_path_len * sizeof(int32_t), e->stream);
-  }
-  if (err == hipSuccess) {
+  Staging st(e, "rna_goal_field_paths");
+  const int32_t* d_starts = host ? st.in(starts, (size_t)n) : starts;
+  // (cells behind a path's end come back as 0; the _device form leaves them as the caller's buffer had them)
+  int32_t* d_paths = host ? st.out(paths, (size_t)n * max_path_len, true) : paths;
+  rna_astar_result* d_res = host ? st.out(results, (size_t)n) : results;
+  if (st.ok())
     hipLaunchKernelGGL(gf_paths_kernel, dim3(n), dim3(64), 0, e->stream, f.field, f.next, d_starts, n, d_paths, max_path_len, d_res,
                        f.rows, f.cols, f.s0, f.s1);
-    err = hipGetLastError();
-  }
-  if (host) {
-    if (err == hipSuccess)
-      err = hipMemcpyAsync(paths, d_paths, (size_t)n * max_path_len * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(results, d_res, (size_t)n * sizeof(rna_astar_result), hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (d_starts) (void)hipFree(d_starts);
-    if (d_paths) (void)hipFree(d_paths);
-    if (d_res) (void)hipFree(d_res);
-  }
-  RNA_HIP(e, err);
-  return RNA_OK;
+  return st.finish();
 }
 
 extern "C" int rna_goal_field_paths(rna_engine* e, const int32_t* starts_host, int n, int32_t* paths_host, int max_path_len,

@@ -73,17 +73,11 @@ extern "C" int rna_to_occupancy_grid_device(rna_engine* e, int layer, float data
 extern "C" int rna_to_occupancy_grid(rna_engine* e, int layer, float data_min, float data_max, int8_t* out_host) {
   if (!e || !out_host) return RNA_EINVAL;
   RNA_ENTER(e);
-  int8_t* d = nullptr;
-  int rc = dev_alloc(e, &d, e->ncell);
-  if (rc != RNA_OK) return rc;
-  rc = rna_to_occupancy_grid_device(e, layer, data_min, data_max, d);
-  hipError_t st = hipSuccess;
-  if (rc == RNA_OK) st = hipMemcpyAsync(out_host, d, e->ncell, hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  dev_free(&d);
-  if (rc != RNA_OK) return rc;
-  if (st != hipSuccess) return fail(e, RNA_EHIP, hipGetErrorString(st));
-  return RNA_OK;
+  Staging st(e, "rna_to_occupancy_grid");
+  int8_t* d = st.out(out_host, e->ncell);
+  if (!st.ok()) return st.finish();
+  const int rc = rna_to_occupancy_grid_device(e, layer, data_min, data_max, d);
+  return rc != RNA_OK ? rc : st.finish();
 }
 
 extern "C" int rna_from_occupancy_grid(rna_engine* e, int layer, const int8_t* data_host) {
@@ -91,18 +85,13 @@ extern "C" int rna_from_occupancy_grid(rna_engine* e, int layer, const int8_t* d
   if (e->geom.start[0] != 0 || e->geom.start[1] != 0)   // the reference resets the geometry in that case (:230-236)
     return fail(e, RNA_ESTATE, "rna_from_occupancy_grid: map has been moved (start index != 0)");
   RNA_ENTER(e);
-  int8_t* d = nullptr;
-  int rc = dev_alloc(e, &d, e->ncell);
-  if (rc != RNA_OK) return rc;
-  hipError_t st = hipMemcpyAsync(d, data_host, e->ncell, hipMemcpyHostToDevice, e->stream);
-  if (st == hipSuccess) {
+  Staging st(e, "rna_from_occupancy_grid");
+  const int8_t* d = st.in(data_host, e->ncell);
+  if (st.ok())
     hipLaunchKernelGGL(from_occupancy_kernel, dim3(grid_for(e->ncell, 256)), dim3(256), 0, e->stream, d, e->ncell,
                        e->layer[layer]);
-    st = hipGetLastError();
-  }
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  dev_free(&d);
-  if (st != hipSuccess) return fail(e, RNA_EHIP, hipGetErrorString(st));
+  const int rc = st.finish();
+  if (rc != RNA_OK) return rc;
   if (layer == RNA_LAYER_MASTER) { e->nbr_all_dirty = true; e->master_diverged = true; }
   if (layer == RNA_LAYER_LASER) e->laser_all_dirty = true;
   e->map_epoch++;
@@ -120,19 +109,14 @@ extern "C" int rna_vfh_hist_msg_batch(rna_engine* e, int n, uint16_t* x_data_hos
   for (int i = 0; i < bins; ++i) x_data_host[i] = (uint16_t)(i * e->vfh.p.sector_angle);
   if (n == 0) return RNA_OK;
   RNA_ENTER(e);
-  uint16_t* d = nullptr;
   const size_t cnt = (size_t)n * bins;
-  int rc = dev_alloc(e, &d, 2 * cnt);
-  if (rc != RNA_OK) return rc;
-  hipLaunchKernelGGL(hist_msg_kernel, dim3(grid_for(cnt, 256)), dim3(256), 0, e->stream, e->vfh.hist, e->vfh.origin, H, n, d,
-                     d + cnt);
-  hipError_t st = hipGetLastError();
-  if (st == hipSuccess) st = hipMemcpyAsync(y_data_host, d, cnt * 2, hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipMemcpyAsync(y_bin_data_host, d + cnt, cnt * 2, hipMemcpyDeviceToHost, e->stream);
-  if (st == hipSuccess) st = hipStreamSynchronize(e->stream);
-  dev_free(&d);
-  if (st != hipSuccess) return fail(e, RNA_EHIP, hipGetErrorString(st));
-  return RNA_OK;
+  Staging st(e, "rna_vfh_hist_msg_batch");
+  uint16_t* d_y = st.out(y_data_host, cnt);
+  uint16_t* d_bin = st.out(y_bin_data_host, cnt);
+  if (st.ok())
+    hipLaunchKernelGGL(hist_msg_kernel, dim3(grid_for(cnt, 256)), dim3(256), 0, e->stream, e->vfh.hist, e->vfh.origin, H, n, d_y,
+                       d_bin);
+  return st.finish();
 }
 
 extern "C" int rna_tailor_plan(const double* plan_xy, int n, unsigned stride, double* out_xy, int* n_out) {

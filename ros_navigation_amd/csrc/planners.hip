@@ -808,51 +808,24 @@ extern "C" int rna_graph_astar_batch(rna_engine* e, int nv, const double* vertex
     adj_v[off[u] + fill[u]] = v; adj_w[off[u] + fill[u]++] = w;
     adj_v[off[v] + fill[v]] = u; adj_w[off[v] + fill[v]++] = w;
   }
-  double *d_loc = nullptr, *d_st = nullptr, *d_paths = nullptr;
-  int *d_off = nullptr, *d_adjv = nullptr, *d_si = nullptr, *d_len = nullptr;
-  float *d_adjw = nullptr, *d_sf = nullptr;
-  int rc = RNA_OK;
-  auto cleanup = [&]() {
-    dev_free(&d_loc); dev_free(&d_st); dev_free(&d_paths); dev_free(&d_off); dev_free(&d_adjv); dev_free(&d_si);
-    dev_free(&d_len); dev_free(&d_adjw); dev_free(&d_sf);
-  };
-#define GA_TRY(x) do { rc = (x); if (rc != RNA_OK) { cleanup(); return rc; } } while (0)
-#define GA_HIP(x) do { if ((x) != hipSuccess) { cleanup(); return fail(e, RNA_EHIP, #x); } } while (0)
-  GA_TRY(dev_alloc(e, &d_loc, (size_t)2 * nv));
-  GA_TRY(dev_alloc(e, &d_st, (size_t)4 * n));
-  GA_TRY(dev_alloc(e, &d_paths, (size_t)2 * max_len * n));
-  GA_TRY(dev_alloc(e, &d_off, (size_t)nv + 1));
-  GA_TRY(dev_alloc(e, &d_adjv, adj_v.size()));
-  GA_TRY(dev_alloc(e, &d_adjw, adj_w.size()));
-  GA_TRY(dev_alloc(e, &d_sf, (size_t)2 * nv * n));
-  GA_TRY(dev_alloc(e, &d_si, (size_t)4 * nv * n));
-  GA_TRY(dev_alloc(e, &d_len, (size_t)n));
-  GA_HIP(hipMemcpyAsync(d_loc, vertex_xy, sizeof(double) * 2 * nv, hipMemcpyHostToDevice, e->stream));
-  GA_HIP(hipMemcpyAsync(d_st, start_target_xy, sizeof(double) * 4 * n, hipMemcpyHostToDevice, e->stream));
-  GA_HIP(hipMemcpyAsync(d_off, off.data(), sizeof(int) * (nv + 1), hipMemcpyHostToDevice, e->stream));
-  GA_HIP(hipMemcpyAsync(d_adjv, adj_v.data(), sizeof(int) * adj_v.size(), hipMemcpyHostToDevice, e->stream));
-  GA_HIP(hipMemcpyAsync(d_adjw, adj_w.data(), sizeof(float) * adj_w.size(), hipMemcpyHostToDevice, e->stream));
-  GraphK G{nv, ne, d_loc, d_off, d_adjv, d_adjw};
-  hipLaunchKernelGGL(graph_astar_kernel, dim3((n + 63) / 64), dim3(64), 0, e->stream, G, d_st, n, d_sf, d_si,
-                     d_paths, max_len, d_len);
-  GA_HIP(hipGetLastError());
-  GA_HIP(hipMemcpyAsync(paths_xy, d_paths, sizeof(double) * 2 * max_len * n, hipMemcpyDeviceToHost, e->stream));
-  GA_HIP(hipMemcpyAsync(path_len, d_len, sizeof(int) * n, hipMemcpyDeviceToHost, e->stream));
-  GA_HIP(hipStreamSynchronize(e->stream));
-#undef GA_TRY
-#undef GA_HIP
-  cleanup();
-  return RNA_OK;
+  Staging st(e, "rna_graph_astar_batch");
+  const GraphK G{nv, ne, st.in(vertex_xy, (size_t)2 * nv), st.in(off.data(), off.size()), st.in(adj_v.data(), adj_v.size()),
+                 st.in(adj_w.data(), adj_w.size())};
+  const double* d_st = st.in(start_target_xy, (size_t)4 * n);
+  float* d_sf = st.scratch<float>((size_t)2 * nv * n);
+  int* d_si = st.scratch<int>((size_t)4 * nv * n);
+  double* d_paths = st.out(paths_xy, (size_t)2 * max_len * n);
+  int* d_len = st.out(path_len, (size_t)n);
+  if (st.ok())
+    hipLaunchKernelGGL(graph_astar_kernel, dim3((n + 63) / 64), dim3(64), 0, e->stream, G, d_st, n, d_sf, d_si, d_paths, max_len, d_len);
+  return st.finish();
 }
 
-static int rrt_launch(rna_engine* e, const rna_rrt_query* q_dev, int n, double* paths_dev, int max_len,
-                      rna_rrt_result* res_dev, double** tx, double** ty, int** tp) {
-  int rc;
-  (void)tx; (void)ty;   // node positions live in LDS; only the parent links go through HBM
-  if ((rc = dev_alloc(e, tp, (size_t)n * RRT_ITER)) != RNA_OK) return rc;
+// the launch of both entry points; tp: RRT_ITER parent links per query (node positions live in LDS, only the links go through HBM)
+static int rrt_launch(rna_engine* e, const rna_rrt_query* q_dev, int n, double* paths_dev, int max_len, rna_rrt_result* res_dev, int* tp) {
   KernelTimer kt(e, RNA_K_RRT);
   hipLaunchKernelGGL(rrt_kernel, dim3(n), dim3(64 * RRT_SPEC), 0, e->stream, e->geom,
-                     e->layer[RNA_LAYER_MASTER], q_dev, n, *tp, paths_dev, max_len, res_dev);
+                     e->layer[RNA_LAYER_MASTER], q_dev, n, tp, paths_dev, max_len, res_dev);
   RNA_HIP(e, hipGetLastError());
 #ifdef RNA_RRT_STATS
   {
@@ -876,12 +849,11 @@ extern "C" int rna_rrt_batch_device(rna_engine* e, const rna_rrt_query* queries,
   if (!e || n < 0 || max_path_len <= 0 || (n > 0 && (!queries || !paths_xy || !results))) return RNA_EINVAL;
   if (n == 0) return RNA_OK;
   RNA_ENTER(e);
-  double *tx = nullptr, *ty = nullptr;
-  int* tp = nullptr;
-  int rc = rrt_launch(e, queries, n, paths_xy, max_path_len, results, &tx, &ty, &tp);
-  if (rc == RNA_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(e, RNA_EHIP, "rrt sync");
-  dev_free(&tx); dev_free(&ty); dev_free(&tp);
-  return rc;
+  Staging st(e, "rna_rrt_batch_device");
+  int* tp = st.scratch<int>((size_t)n * RRT_ITER);
+  if (!st.ok()) return st.finish();
+  const int rc = rrt_launch(e, queries, n, paths_xy, max_path_len, results, tp);
+  return rc != RNA_OK ? rc : st.finish();
 }
 
 extern "C" int rna_rrt_batch(rna_engine* e, const rna_rrt_query* queries_host, int n, double* paths_xy_host,
@@ -890,24 +862,12 @@ extern "C" int rna_rrt_batch(rna_engine* e, const rna_rrt_query* queries_host, i
     return RNA_EINVAL;
   if (n == 0) return RNA_OK;
   RNA_ENTER(e);
-  rna_rrt_query* dq = nullptr;
-  rna_rrt_result* dr = nullptr;
-  double *dp = nullptr, *tx = nullptr, *ty = nullptr;
-  int* tp = nullptr;
-  int rc = RNA_OK;
-  auto cleanup = [&]() { dev_free(&dq); dev_free(&dr); dev_free(&dp); dev_free(&tx); dev_free(&ty); dev_free(&tp); };
-  if ((rc = dev_alloc(e, &dq, (size_t)n)) != RNA_OK || (rc = dev_alloc(e, &dr, (size_t)n)) != RNA_OK ||
-      (rc = dev_alloc(e, &dp, (size_t)n * max_path_len * 2)) != RNA_OK) { cleanup(); return rc; }
-  if (hipMemcpyAsync(dq, queries_host, sizeof(rna_rrt_query) * n, hipMemcpyHostToDevice, e->stream) != hipSuccess) {
-    cleanup(); return fail(e, RNA_EHIP, "rrt H2D");
-  }
-  rc = rrt_launch(e, dq, n, dp, max_path_len, dr, &tx, &ty, &tp);
-  if (rc == RNA_OK) {
-    if (hipMemcpyAsync(results_host, dr, sizeof(rna_rrt_result) * n, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-        hipMemcpyAsync(paths_xy_host, dp, sizeof(double) * 2 * max_path_len * n, hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-        hipStreamSynchronize(e->stream) != hipSuccess)
-      rc = fail(e, RNA_EHIP, "rrt D2H");
-  }
-  cleanup();
-  return rc;
+  Staging st(e, "rna_rrt_batch");
+  const rna_rrt_query* dq = st.in(queries_host, (size_t)n);
+  rna_rrt_result* dr = st.out(results_host, (size_t)n);
+  double* dp = st.out(paths_xy_host, (size_t)n * max_path_len * 2);
+  int* tp = st.scratch<int>((size_t)n * RRT_ITER);
+  if (!st.ok()) return st.finish();
+  const int rc = rrt_launch(e, dq, n, dp, max_path_len, dr, tp);
+  return rc != RNA_OK ? rc : st.finish();
 }

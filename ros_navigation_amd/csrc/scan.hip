@@ -200,24 +200,16 @@ static int scan_to_rays_device_t(rna_engine* e, const Scan* scans_device, int n_
     RNA_HIP(e, hipMemsetAsync(n_rays_device, 0, sizeof(int), e->stream));
     return RNA_OK;
   }
-  rna_ray* staged = nullptr;
-  int* counts = nullptr;
-  int rc = dev_alloc(e, &staged, (size_t)n_scans * max_beams_per_scan);
-  if (rc == RNA_OK) rc = dev_alloc(e, &counts, (size_t)n_scans);
-  if (rc == RNA_OK) {
+  Staging st(e, "rna_scan_to_rays");
+  rna_ray* staged = st.scratch<rna_ray>((size_t)n_scans * max_beams_per_scan);
+  int* counts = st.scratch<int>((size_t)n_scans);
+  if (st.ok()) {
     hipLaunchKernelGGL(scan_to_rays_kernel<Scan>, dim3(n_scans), dim3(SCAN_THREADS), 0, e->stream, scans_device, ranges_device,
                        max_beams_per_scan, staged, counts);
     hipLaunchKernelGGL(scan_pack_kernel, dim3(1), dim3(256), 0, e->stream, staged, counts, n_scans, max_beams_per_scan,
                        rays_device, max_rays, n_rays_device);
-    if (hipGetLastError() != hipSuccess) rc = fail(e, RNA_EHIP, "rna_scan_to_rays: launch failed");
   }
-  // the staging buffers are freed once the kernels are done (hipFree synchronises)
-  hipError_t st = hipStreamSynchronize(e->stream);
-  dev_free(&staged);
-  dev_free(&counts);
-  if (rc != RNA_OK) return rc;
-  if (st != hipSuccess) return fail(e, RNA_EHIP, hipGetErrorString(st));
-  return RNA_OK;
+  return st.finish();   // (the two buffers are freed once the kernels are done)
 }
 
 template <class Scan>
@@ -236,30 +228,17 @@ static int scan_to_rays_host_t(rna_engine* e, const Scan* scans_host, int n_scan
   }
   if (max_beams > SCAN_MAX_BEAMS) return fail(e, RNA_EINVAL, "rna_scan_to_rays: more than 8192 beams per scan");
   RNA_ENTER(e);
-  Scan* d_scans = nullptr;
-  float* d_ranges = nullptr;
-  rna_ray* d_rays = nullptr;
-  int* d_n = nullptr;
-  int rc = dev_alloc(e, &d_scans, (size_t)n_scans);
-  if (rc == RNA_OK) rc = dev_alloc(e, &d_ranges, n_ranges_total ? n_ranges_total : 1);
-  if (rc == RNA_OK) rc = dev_alloc(e, &d_rays, (size_t)(max_rays ? max_rays : 1));
-  if (rc == RNA_OK) rc = dev_alloc(e, &d_n, (size_t)1);
-  hipError_t st = hipSuccess;
-  if (rc == RNA_OK) {
-    st = hipMemcpyAsync(d_scans, scans_host, sizeof(Scan) * n_scans, hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess && n_ranges_total)
-      st = hipMemcpyAsync(d_ranges, ranges_host, sizeof(float) * n_ranges_total, hipMemcpyHostToDevice, e->stream);
-    if (st == hipSuccess) rc = scan_to_rays_device_t<Scan>(e, d_scans, n_scans, d_ranges, max_beams, d_rays, max_rays, d_n);
-    if (st == hipSuccess && rc == RNA_OK) st = hipMemcpyAsync(n_rays, d_n, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-    if (st == hipSuccess && rc == RNA_OK) st = hipStreamSynchronize(e->stream);
-    if (st == hipSuccess && rc == RNA_OK) {
-      const int have = *n_rays < max_rays ? *n_rays : max_rays;
-      if (have > 0) st = hipMemcpy(rays_host, d_rays, sizeof(rna_ray) * have, hipMemcpyDeviceToHost);
-    }
-  }
-  dev_free(&d_scans); dev_free(&d_ranges); dev_free(&d_rays); dev_free(&d_n);
-  if (rc != RNA_OK) return rc;
-  if (st != hipSuccess) return fail(e, RNA_EHIP, hipGetErrorString(st));
+  Staging st(e, "rna_scan_to_rays");
+  const Scan* d_scans = st.in(scans_host, (size_t)n_scans);
+  const float* d_ranges = st.in(ranges_host, n_ranges_total);
+  rna_ray* d_rays = st.scratch<rna_ray>((size_t)max_rays);
+  int* d_n = st.out(n_rays, 1);
+  if (!st.ok()) return st.finish();
+  int rc = scan_to_rays_device_t<Scan>(e, d_scans, n_scans, d_ranges, max_beams, d_rays, max_rays, d_n);
+  if (rc != RNA_OK || (rc = st.finish()) != RNA_OK) return rc;
+  // the count is here: only the rays that exist come back
+  const int have = *n_rays < max_rays ? *n_rays : max_rays;
+  if (have > 0) RNA_HIP(e, hipMemcpy(rays_host, d_rays, sizeof(rna_ray) * have, hipMemcpyDeviceToHost));
   if (*n_rays > max_rays) return fail(e, RNA_ECAPACITY, "rna_scan_to_rays: max_rays too small (n_rays holds the required count)");
   return RNA_OK;
 }

@@ -217,43 +217,19 @@ int shortcut_paths(rna_engine* e, const int32_t* paths, const rna_astar_result* 
       for (int d = 0; d < a.depth && d < AstarDevice::MAX_DEPTH; ++d)
         if (a.stage[d].busy && a.stage[d].done) RNA_HIP(e, hipStreamWaitEvent(e->stream, a.stage[d].done, 0));
   }
-  const int32_t* d_paths = paths;
-  const rna_astar_result* d_res = results;
-  int32_t *d_wp = waypoints, *h_paths = nullptr, *h_wp = nullptr;
-  rna_astar_result* h_res = nullptr;
-  rna_shortcut_result *d_out = out, *h_out = nullptr;
-  hipError_t err = hipSuccess;
-  if (host) {
-    const size_t np = (size_t)n * max_path_len, nwp = (size_t)n * max_waypoints;
-    err = hipMalloc(&h_paths, np * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc(&h_res, (size_t)n * sizeof(rna_astar_result));
-    if (err == hipSuccess) err = hipMalloc(&h_wp, nwp * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc(&h_out, (size_t)n * sizeof(rna_shortcut_result));
-    if (err == hipSuccess) err = hipMemcpyAsync(h_paths, paths, np * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(h_res, results, (size_t)n * sizeof(rna_astar_result), hipMemcpyHostToDevice, e->stream);
-    // (slots behind the last way point come back as 0; the _device form leaves them as the caller's buffer had them)
-    if (err == hipSuccess) err = hipMemsetAsync(h_wp, 0, nwp * sizeof(int32_t), e->stream);
-    d_paths = h_paths; d_res = h_res; d_wp = h_wp; d_out = h_out;
-  }
-  if (err == hipSuccess) {
+  Staging st(e, "rna_shortcut_paths");
+  const int32_t* d_paths = host ? st.in(paths, (size_t)n * max_path_len) : paths;
+  const rna_astar_result* d_res = host ? st.in(results, (size_t)n) : results;
+  // (slots behind the last way point come back as 0; the _device form leaves them as the caller's buffer had them)
+  int32_t* d_wp = host ? st.out(waypoints, (size_t)n * max_waypoints, true) : waypoints;
+  rna_shortcut_result* d_out = host ? st.out(out, (size_t)n) : out;
+  if (st.ok()) {
     const Geom& g = e->geom;
     hipLaunchKernelGGL(keep ? shortcut_kernel<true> : shortcut_kernel<false>, dim3(n), dim3(64), lds, e->stream, d_paths, d_res, n,
                        max_path_len, max_span, e->nbr, keep ? e->clearance.clr : (const uint16_t*)nullptr, d_wp, max_waypoints, d_out,
                        g.size[0], g.size[1], g.start[0], g.start[1]);
-    err = hipGetLastError();
   }
-  if (host) {
-    if (err == hipSuccess)
-      err = hipMemcpyAsync(waypoints, h_wp, (size_t)n * max_waypoints * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(out, h_out, (size_t)n * sizeof(rna_shortcut_result), hipMemcpyDeviceToHost, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (h_paths) (void)hipFree(h_paths);
-    if (h_res) (void)hipFree(h_res);
-    if (h_wp) (void)hipFree(h_wp);
-    if (h_out) (void)hipFree(h_out);
-  }
-  RNA_HIP(e, err);
-  return RNA_OK;
+  return st.finish();
 }
 
 }  // namespace
