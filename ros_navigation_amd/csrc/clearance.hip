@@ -95,7 +95,7 @@ int clearance_refresh(rna_engine* e, int R) {
                      g.start[0], g.start[1]);
   RNA_HIP(e, hipGetLastError());
   c.R = R;
-  c.epoch = e->map_epoch;
+  c.epoch = e->map.epoch;
   return RNA_OK;
 }
 
@@ -125,6 +125,6 @@ extern "C" void* rna_clearance_device_ptr(rna_engine* e) { return (e && e->clear
 extern "C" int rna_clearance_info_get(const rna_engine* e, int* max_cells, int* stale) {
   if (!e || !max_cells || !stale) return RNA_EINVAL;
   *max_cells = e->clearance.R;
-  *stale = (e->clearance.R > 0 && e->clearance.epoch != e->map_epoch) ? 1 : 0;
+  *stale = (e->clearance.R > 0 && e->clearance.epoch != e->map.epoch) ? 1 : 0;
   return RNA_OK;
 }

@@ -182,6 +182,23 @@ static int fill_layer(rna_engine* e, float* p, float v) {
   return RNA_OK;
 }
 
+// words of a tile-flag array (dirty_tiles, last_dirty): one byte per tile, rounded up
+static size_t flag_words(const rna_engine* e) { return ((size_t)e->tiles_i * e->tiles_j + 3) / 4; }
+
+// A non-blocking stream of the highest priority (of priority 0: `plain`); or, developer knob `knob`=n with n below the CU
+// count, a stream that may only use the first n CUs of the mask order.
+static hipError_t create_stream(const rna_engine* e, const char* knob, bool plain, hipStream_t* out) {
+  int prio_lo = 0, prio_hi = 0;   // numerically lower = higher priority
+  (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+  int only = 0;
+  if (const char* m = getenv(knob)) only = atoi(m);
+  if (only <= 0 || only >= e->cu_count) return hipStreamCreateWithPriority(out, hipStreamNonBlocking, plain ? 0 : prio_hi);
+  uint32_t mask[16] = {};
+  for (int c = 0; c < only && c < 512; ++c) mask[c >> 5] |= 1u << (c & 31);
+  const int words = (e->cu_count + 31) / 32 < 16 ? (e->cu_count + 31) / 32 : 16;
+  return hipExtStreamCreateWithCUMask(out, (uint32_t)words, mask);
+}
+
 extern "C" int rna_abi_version(void) { return RNA_ABI_VERSION; }
 
 extern "C" const char* rna_last_error(const rna_engine* e) { return e ? e->err.c_str() : "null engine"; }
@@ -219,35 +236,20 @@ extern "C" int rna_create(rna_engine** out, double length_x, double length_y, do
   int rc = RNA_OK;
   auto bail = [&](int code) { rna_destroy(e); return code; };
   if (hipSetDevice(device_id) != hipSuccess) return bail(RNA_EHIP);
-  {
-    int prio_lo = 0, prio_hi = 0;   // numerically lower = higher priority
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (getenv("RNA_NO_STREAM_PRIORITY")) prio_lo = prio_hi = 0;
-    // developer knob RNA_ENGINE_CU_MASK=n: the engine stream may only use the first n CUs of the mask order (the CUs
-    // the pipelined search streams leave free, astar.hip) -- its short kernels then never land next to search
-    // workgroups on a CU whose issue slots they fill
-    int only = 0;
-    if (const char* m = getenv("RNA_ENGINE_CU_MASK")) only = atoi(m);
-    hipDeviceProp_t prop;
-    if (only > 0 && hipGetDeviceProperties(&prop, device_id) == hipSuccess && only < prop.multiProcessorCount) {
-      uint32_t mask[16] = {};
-      for (int c = 0; c < only && c < 512; ++c) mask[c >> 5] |= 1u << (c & 31);
-      const int words = (prop.multiProcessorCount + 31) / 32 < 16 ? (prop.multiProcessorCount + 31) / 32 : 16;
-      if (hipExtStreamCreateWithCUMask(&e->stream, (uint32_t)words, mask) != hipSuccess) return bail(RNA_EHIP);
-    } else if (hipStreamCreateWithPriority(&e->stream, hipStreamNonBlocking, prio_hi) != hipSuccess) return bail(RNA_EHIP);
-  }
+  // developer knob RNA_ENGINE_CU_MASK=n: the CUs the pipelined search streams leave free (astar.hip) -- the engine stream's
+  // short kernels then never land next to search workgroups on a CU whose issue slots they fill
+  if (create_stream(e, "RNA_ENGINE_CU_MASK", getenv("RNA_NO_STREAM_PRIORITY") != nullptr, &e->stream) != hipSuccess) return bail(RNA_EHIP);
   for (int l = 0; l < RNA_NUM_LAYERS; ++l) {
     if ((rc = dev_alloc(e, &e->layer[l], e->ncell)) != RNA_OK) return bail(rc);
     // GridMap::setGeometry -> clearAll(): every layer starts as NaN (gmc/src/GridMap.cpp:62)
     if ((rc = fill_layer(e, e->layer[l], std::numeric_limits<float>::quiet_NaN())) != RNA_OK) return bail(rc);
   }
-  const size_t words = ((size_t)e->tiles_i * e->tiles_j + 3) / 4;  // one byte per tile, rounded to words
+  const size_t words = flag_words(e);
   if ((rc = dev_alloc(e, &e->dirty_tiles, words)) != RNA_OK) return bail(rc);
   if (hipMemsetAsync(e->dirty_tiles, 0, words * sizeof(unsigned), e->stream) != hipSuccess) return bail(RNA_EHIP);
   if ((rc = dev_alloc(e, &e->last_dirty, words)) != RNA_OK) return bail(rc);
   if (hipMemsetAsync(e->last_dirty, 0, words * sizeof(unsigned), e->stream) != hipSuccess) return bail(RNA_EHIP);
-  if ((rc = dev_alloc(e, &e->nbr, e->ncell)) != RNA_OK) return bail(rc);
-  e->nbr_all_dirty = true;
+  if ((rc = dev_alloc(e, &e->nbr, e->ncell)) != RNA_OK) return bail(rc);   // (a fresh MapState has the masks waiting)
   if (hipStreamSynchronize(e->stream) != hipSuccess) return bail(RNA_EHIP);
   *out = e;
   return RNA_OK;
@@ -291,20 +293,12 @@ extern "C" int rna_get_geometry(const rna_engine* e, rna_geometry* o) {
   return RNA_OK;
 }
 
-static void layer_changed(rna_engine* e, int layer) {
-  e->map_epoch++;
-  // master written directly (upload, fill, fromOccupancyGrid, a caller's device pointer): it no longer equals laser
-  // outside the dirty tiles, so the next compose has to be the reference's whole-layer copy (map_provider.cpp:221)
-  if (layer == RNA_LAYER_MASTER) { e->nbr_all_dirty = true; e->master_diverged = true; }
-  if (layer == RNA_LAYER_LASER) e->laser_all_dirty = true;
-}
-
 extern "C" int rna_layer_upload(rna_engine* e, int layer, const float* host, size_t n) {
   if (!e || !host || layer < 0 || layer >= RNA_NUM_LAYERS || n != e->ncell) return RNA_EINVAL;
   RNA_ENTER(e);
   RNA_HIP(e, hipMemcpyAsync(e->layer[layer], host, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
   RNA_HIP(e, hipStreamSynchronize(e->stream));
-  layer_changed(e, layer);
+  e->map.layer_written(layer);
   return RNA_OK;
 }
 
@@ -320,13 +314,13 @@ extern "C" int rna_layer_fill(rna_engine* e, int layer, float value) {
   if (!e || layer < 0 || layer >= RNA_NUM_LAYERS) return RNA_EINVAL;
   RNA_ENTER(e);
   int rc = fill_layer(e, e->layer[layer], value);
-  layer_changed(e, layer);
+  e->map.layer_written(layer);
   return rc;
 }
 
 extern "C" void* rna_layer_device_ptr(rna_engine* e, int layer) {
   if (!e || layer < 0 || layer >= RNA_NUM_LAYERS) return nullptr;
-  layer_changed(e, layer);  // the caller may write through the pointer
+  e->map.layer_written(layer);  // the caller may write through the pointer
   return e->layer[layer];
 }
 
@@ -348,12 +342,12 @@ static int region_copy(rna_engine* e, int layer, int i0, int ni, int j0, int nj,
     if (tracked) {   // per-tile bookkeeping instead of "everything changed": the next compose refreshes these tiles
       const int ta0 = i0 / TILE, ta1 = (i0 + ni - 1) / TILE + 1, tb0 = j0 / TILE, tb1 = (j0 + nj - 1) / TILE + 1;
       const int nt = (ta1 - ta0) * (tb1 - tb0);
-      e->map_epoch++;
+      e->map.tiles_written();
       hipLaunchKernelGGL(mark_tiles_kernel, dim3((nt + 255) / 256), dim3(256), 0, e->stream, e->dirty_tiles, e->tiles_i, ta0,
                          ta1, tb0, tb1);
       RNA_HIP(e, hipGetLastError());
     } else {
-      layer_changed(e, layer);
+      e->map.layer_written(layer);
     }
   }
   RNA_HIP(e, hipStreamSynchronize(e->stream));
@@ -405,7 +399,9 @@ extern "C" int rna_last_dirty_tiles(rna_engine* e, uint8_t* flags_host, size_t n
   return RNA_OK;
 }
 
-static int stage_tile_list(rna_engine* e, const int32_t* tiles_host, int n) {
+// a tile list in host memory: checked, copied to e->tile_list on the engine stream, and *tiles then names that copy
+static int stage_tile_list(rna_engine* e, const int32_t** tiles, int n) {
+  const int32_t* tiles_host = *tiles;
   const int ntile = e->tiles_i * e->tiles_j;
   for (int k = 0; k < n; ++k)
     if (tiles_host[k] < 0 || tiles_host[k] >= ntile) return rna::fail(e, RNA_EINVAL, "tile index outside the map");
@@ -417,6 +413,7 @@ static int stage_tile_list(rna_engine* e, const int32_t* tiles_host, int n) {
     e->tile_list_cap = cap;
   }
   RNA_HIP(e, hipMemcpyAsync(e->tile_list, tiles_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  *tiles = e->tile_list;
   return RNA_OK;
 }
 
@@ -424,38 +421,50 @@ static bool window_ok(const rna_engine* e, int i0, int ni, int j0, int nj) {
   return i0 >= 0 && j0 >= 0 && ni > 0 && nj > 0 && i0 + ni <= e->geom.size[0] && j0 + nj <= e->geom.size[1];
 }
 
-extern "C" int rna_layer_pack_tiles(rna_engine* e, int layer, const int32_t* tiles_host, int n, int i0, int ni, int j0,
-                                    int nj, float* dense_device) {
-  if (!e || layer < 0 || layer >= RNA_NUM_LAYERS || n < 0 || (n > 0 && (!tiles_host || !dense_device))) return RNA_EINVAL;
+// The two calls, each with its list in host memory (staged into e->tile_list; the call returns with the stream drained) or
+// in device memory (asynchronous on the engine's stream).
+static int pack_tiles(rna_engine* e, int layer, const int32_t* tiles, bool host_list, int n, int i0, int ni, int j0, int nj,
+                      float* dense_device) {
+  if (!e || layer < 0 || layer >= RNA_NUM_LAYERS || n < 0 || (n > 0 && (!tiles || !dense_device))) return RNA_EINVAL;
   if (n == 0) return RNA_OK;
   if (!window_ok(e, i0, ni, j0, nj)) return rna::fail(e, RNA_EINVAL, "window outside the map");
   RNA_ENTER(e);
-  int rc = stage_tile_list(e, tiles_host, n);
-  if (rc != RNA_OK) return rc;
-  hipLaunchKernelGGL(pack_tiles_kernel, dim3(n), dim3(256), 0, e->stream, e->layer[layer], e->geom.size[0], e->tiles_i,
-                     e->tile_list, i0, i0 + ni, j0, j0 + nj, dense_device);
+  int rc = RNA_OK;
+  if (host_list && (rc = stage_tile_list(e, &tiles, n)) != RNA_OK) return rc;
+  hipLaunchKernelGGL(pack_tiles_kernel, dim3(n), dim3(256), 0, e->stream, e->layer[layer], e->geom.size[0], e->tiles_i, tiles, i0,
+                     i0 + ni, j0, j0 + nj, dense_device);
   RNA_HIP(e, hipGetLastError());
-  RNA_HIP(e, hipStreamSynchronize(e->stream));
+  if (host_list) RNA_HIP(e, hipStreamSynchronize(e->stream));
   return RNA_OK;
 }
 
-extern "C" int rna_layers_unpack_tiles(rna_engine* e, int layer_a, int layer_b, const int32_t* tiles_host, int n, int i0,
-                                       int ni, int j0, int nj, const float* dense_device) {
+static int unpack_tiles(rna_engine* e, int layer_a, int layer_b, const int32_t* tiles, bool host_list, int n, int i0, int ni, int j0,
+                        int nj, const float* dense_device) {
   if (!e || layer_a < 0 || layer_a >= RNA_NUM_LAYERS || layer_b >= RNA_NUM_LAYERS || layer_b == layer_a || n < 0 ||
-      (n > 0 && (!tiles_host || !dense_device)))
+      (n > 0 && (!tiles || !dense_device)))
     return RNA_EINVAL;
   if (n == 0) return RNA_OK;
   if (!window_ok(e, i0, ni, j0, nj)) return rna::fail(e, RNA_EINVAL, "window outside the map");
   RNA_ENTER(e);
-  e->map_epoch++;
-  int rc = stage_tile_list(e, tiles_host, n);
-  if (rc != RNA_OK) return rc;
+  e->map.tiles_written();   // (before the list is looked at: a refused list has counted too)
+  int rc = RNA_OK;
+  if (host_list && (rc = stage_tile_list(e, &tiles, n)) != RNA_OK) return rc;
   hipLaunchKernelGGL(unpack_tiles_kernel, dim3(n), dim3(256), 0, e->stream, e->layer[layer_a],
-                     layer_b >= 0 ? e->layer[layer_b] : (float*)nullptr, e->geom.size[0], e->tiles_i, e->tile_list, i0,
-                     i0 + ni, j0, j0 + nj, dense_device, e->dirty_tiles);
+                     layer_b >= 0 ? e->layer[layer_b] : (float*)nullptr, e->geom.size[0], e->tiles_i, tiles, i0, i0 + ni, j0, j0 + nj,
+                     dense_device, e->dirty_tiles);
   RNA_HIP(e, hipGetLastError());
-  RNA_HIP(e, hipStreamSynchronize(e->stream));
+  if (host_list) RNA_HIP(e, hipStreamSynchronize(e->stream));
   return RNA_OK;
+}
+
+extern "C" int rna_layer_pack_tiles(rna_engine* e, int layer, const int32_t* tiles_host, int n, int i0, int ni, int j0,
+                                    int nj, float* dense_device) {
+  return pack_tiles(e, layer, tiles_host, true, n, i0, ni, j0, nj, dense_device);
+}
+
+extern "C" int rna_layers_unpack_tiles(rna_engine* e, int layer_a, int layer_b, const int32_t* tiles_host, int n, int i0,
+                                       int ni, int j0, int nj, const float* dense_device) {
+  return unpack_tiles(e, layer_a, layer_b, tiles_host, true, n, i0, ni, j0, nj, dense_device);
 }
 
 // Device-side forms of the three calls above for hosts that drive the exchange themselves (csrc/rccl_tiled.hip): no
@@ -474,29 +483,27 @@ extern "C" int rna_last_dirty_tiles_device(rna_engine* e, int i0, int ni, int j0
 
 extern "C" int rna_layer_pack_tiles_device(rna_engine* e, int layer, const int32_t* tiles_device, int n, int i0, int ni, int j0,
                                            int nj, float* dense_device) {
-  if (!e || layer < 0 || layer >= RNA_NUM_LAYERS || n < 0 || (n > 0 && (!tiles_device || !dense_device))) return RNA_EINVAL;
-  if (n == 0) return RNA_OK;
-  if (!window_ok(e, i0, ni, j0, nj)) return rna::fail(e, RNA_EINVAL, "window outside the map");
-  RNA_ENTER(e);
-  hipLaunchKernelGGL(pack_tiles_kernel, dim3(n), dim3(256), 0, e->stream, e->layer[layer], e->geom.size[0], e->tiles_i,
-                     tiles_device, i0, i0 + ni, j0, j0 + nj, dense_device);
-  RNA_HIP(e, hipGetLastError());
-  return RNA_OK;
+  return pack_tiles(e, layer, tiles_device, false, n, i0, ni, j0, nj, dense_device);
 }
 
 extern "C" int rna_layers_unpack_tiles_device(rna_engine* e, int layer_a, int layer_b, const int32_t* tiles_device, int n, int i0,
                                               int ni, int j0, int nj, const float* dense_device) {
-  if (!e || layer_a < 0 || layer_a >= RNA_NUM_LAYERS || layer_b >= RNA_NUM_LAYERS || layer_b == layer_a || n < 0 ||
-      (n > 0 && (!tiles_device || !dense_device)))
-    return RNA_EINVAL;
-  if (n == 0) return RNA_OK;
-  if (!window_ok(e, i0, ni, j0, nj)) return rna::fail(e, RNA_EINVAL, "window outside the map");
-  RNA_ENTER(e);
-  e->map_epoch++;
-  hipLaunchKernelGGL(unpack_tiles_kernel, dim3(n), dim3(256), 0, e->stream, e->layer[layer_a],
-                     layer_b >= 0 ? e->layer[layer_b] : (float*)nullptr, e->geom.size[0], e->tiles_i, tiles_device, i0,
-                     i0 + ni, j0, j0 + nj, dense_device, e->dirty_tiles);
-  RNA_HIP(e, hipGetLastError());
+  return unpack_tiles(e, layer_a, layer_b, tiles_device, false, n, i0, ni, j0, nj, dense_device);
+}
+
+// The tail of a clone or a submap, its layers' copies enqueued on the parent's stream (err: their first failure): once they have
+// arrived the child plans for the same robot at the same clearance cost, and its masks and its next compose start from nothing.
+static int adopt(rna_engine* parent, rna_engine* c, hipError_t err, rna_engine** out) {
+  if (err == hipSuccess) err = hipStreamSynchronize(parent->stream);
+  if (err != hipSuccess) {
+    rna_destroy(c);
+    RNA_HIP(parent, err);
+  }
+  c->map.cloned();
+  c->robot_r = parent->robot_r;
+  c->gfield.cost_n = parent->gfield.cost_n;
+  memcpy(c->gfield.cost_tab, parent->gfield.cost_tab, sizeof(c->gfield.cost_tab));
+  *out = c;
   return RNA_OK;
 }
 
@@ -523,18 +530,8 @@ extern "C" int rna_create_submap(rna_engine* parent, double px, double py, doubl
                        c->layer[l]);
     err = hipGetLastError();
   }
-  if (err == hipSuccess) err = hipStreamSynchronize(parent->stream);
-  if (err != hipSuccess) {
-    rna_destroy(c);
-    RNA_HIP(parent, err);
-  }
-  c->nbr_all_dirty = true;
-  c->laser_all_dirty = true;
-  c->robot_r = parent->robot_r;
-  c->gfield.cost_n = parent->gfield.cost_n;
-  memcpy(c->gfield.cost_tab, parent->gfield.cost_tab, sizeof(c->gfield.cost_tab));
-  *out = c;
-  return 1;
+  rc = adopt(parent, c, err, out);
+  return rc == RNA_OK ? 1 : rc;
 }
 
 // GridMap copy (`map = map_` of MapProvider::getMap, mc/src/map_provider.cpp:120-125): a new engine on the same
@@ -554,18 +551,7 @@ extern "C" int rna_clone(rna_engine* src, rna_engine** out) {
   hipError_t err = hipSetDevice(src->device);
   for (int l = 0; l < RNA_NUM_LAYERS && err == hipSuccess; ++l)
     err = hipMemcpyAsync(c->layer[l], src->layer[l], src->ncell * sizeof(float), hipMemcpyDeviceToDevice, src->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(src->stream);
-  if (err != hipSuccess) {
-    rna_destroy(c);
-    RNA_HIP(src, err);
-  }
-  c->nbr_all_dirty = true;
-  c->laser_all_dirty = true;
-  c->robot_r = src->robot_r;
-  c->gfield.cost_n = src->gfield.cost_n;
-  memcpy(c->gfield.cost_tab, src->gfield.cost_tab, sizeof(c->gfield.cost_tab));
-  *out = c;
-  return RNA_OK;
+  return adopt(src, c, err, out);
 }
 
 extern "C" int rna_get_submap(rna_engine* e, int layer, double px, double py, double lx, double ly, float* out_host,
@@ -673,20 +659,8 @@ namespace rna {
 
 int side_stream(rna_engine* e, hipStream_t* out) {
   if (!e->vfh_stream) {
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    // developer knob RNA_SIDE_CU_MASK=n: the side stream (VFH+, mask snapshots, launch orders) may only use the first n CUs of
-    // the mask order, like RNA_ENGINE_CU_MASK for the engine stream
-    int only = 0;
-    if (const char* m = getenv("RNA_SIDE_CU_MASK")) only = atoi(m);
-    if (only > 0 && only < e->cu_count) {
-      uint32_t mask[16] = {};
-      const int words = (e->cu_count + 31) / 32 < 16 ? (e->cu_count + 31) / 32 : 16;
-      for (int c = 0; c < only && c < 512; ++c) mask[c >> 5] |= 1u << (c & 31);
-      RNA_HIP(e, hipExtStreamCreateWithCUMask(&e->vfh_stream, (uint32_t)words, mask));
-    } else {
-      RNA_HIP(e, hipStreamCreateWithPriority(&e->vfh_stream, hipStreamNonBlocking, prio_hi));
-    }
+    // developer knob RNA_SIDE_CU_MASK=n for the side stream (VFH+, mask snapshots, launch orders), like RNA_ENGINE_CU_MASK
+    RNA_HIP(e, create_stream(e, "RNA_SIDE_CU_MASK", false, &e->vfh_stream));
     RNA_HIP(e, hipEventCreateWithFlags(&e->ev_vfh_go, hipEventDisableTiming));
     RNA_HIP(e, hipEventCreateWithFlags(&e->ev_vfh_done, hipEventDisableTiming));
   }
@@ -732,83 +706,74 @@ int profile_flush(rna_engine* e) {
   return RNA_OK;
 }
 
-// Recompute A* neighbour masks where the master layer changed.
+// Rebuild the A* neighbour masks from the master layer if they wait for it.
 int map_prepare_nbr(rna_engine* e) {
-  if (!e->nbr_all_dirty) return RNA_OK;
-  { const int rc = side_join(e); if (rc != RNA_OK) return rc; }   // snapshots in flight read the masks this rebuilds
+  if (!e->map.masks_waiting()) return RNA_OK;
+  int rc = side_join(e);   // snapshots in flight read the masks this rebuilds
+  if (rc != RNA_OK) return rc;
   if (e->robot_r > 0.0) {   // robot radius: the blocked set of the disc (footprint.hip)
-    const int rc = footprint_refresh(e, 1);
-    if (rc != RNA_OK) return rc;
-    e->nbr_all_dirty = false;
-    return RNA_OK;
+    if ((rc = footprint_refresh(e, 1)) != RNA_OK) return rc;
+  } else {
+    KernelTimer kt(e, RNA_K_NBRMASK);
+    hipLaunchKernelGGL(nbr_mask_tiles_kernel, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream, e->nbr,
+                       e->layer[RNA_LAYER_MASTER], e->dirty_tiles, 1, e->geom.size[0], e->geom.size[1], e->tiles_i,
+                       e->tiles_j, e->geom.start[0], e->geom.start[1]);
+    RNA_HIP(e, hipGetLastError());
   }
-  KernelTimer kt(e, RNA_K_NBRMASK);
-  hipLaunchKernelGGL(nbr_mask_tiles_kernel, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream, e->nbr,
-                     e->layer[RNA_LAYER_MASTER], e->dirty_tiles, 1, e->geom.size[0], e->geom.size[1], e->tiles_i,
-                     e->tiles_j, e->geom.start[0], e->geom.start[1]);
-  RNA_HIP(e, hipGetLastError());
-  e->nbr_all_dirty = false;
+  e->map.masks_rebuilt();
   return RNA_OK;
 }
 
 }  // namespace rna
 
+// MapProvider::composeMasterMapFromLayerdMap.  What to enqueue is MapState::plan_compose's decision; the order is fixed:
+// the copy, the mask refresh (it reads the dirty flags), last_dirty, then the flags are cleared.
 extern "C" int rna_compose_master(rna_engine* e, int mode) {
   if (!e || (mode != 0 && mode != 1)) return RNA_EINVAL;
   RNA_ENTER(e);
-  e->map_epoch++;
-  const size_t words = ((size_t)e->tiles_i * e->tiles_j + 3) / 4;  // one byte per tile, rounded to words
-  const bool full = (mode == 1) || e->laser_all_dirty || e->master_diverged;
-  const bool moved = e->geom.start[0] != 0 || e->geom.start[1] != 0;
-  if (!full && !moved && !e->nbr_all_dirty && e->robot_r == 0.0) {
-    // the usual case of the replan loop: dirty tiles only, masks valid before -- one launch, and the two flag arrays
-    // swap roles (what this compose consumed = rna_last_dirty_tiles; the other one, cleared by the launch, is marked next)
-    KernelTimer kt(e, RNA_K_COMPOSE);
-    static const int wgs_per_cu = [] { const char* v = getenv("RNA_COMPOSE_WGS_PER_CU"); const int n = v ? atoi(v) : 0; return n > 0 ? n : 16; }();   // developer knob
-    hipLaunchKernelGGL(compose_nbr_tiles_kernel, dim3(std::min(e->tiles_i * e->tiles_j, wgs_per_cu * e->cu_count)), dim3(256), 0, e->stream, e->nbr,
-                       e->layer[RNA_LAYER_MASTER], e->layer[RNA_LAYER_LASER], e->dirty_tiles, e->last_dirty, e->geom.size[0],
-                       e->geom.size[1], e->tiles_i, e->tiles_j);
-    RNA_HIP(e, hipGetLastError());
-    std::swap(e->dirty_tiles, e->last_dirty);
-    return RNA_OK;
-  }
+  e->map.compose_begins();
+  const ComposePlan plan = e->map.plan_compose(mode, e->geom.start[0] != 0 || e->geom.start[1] != 0, e->robot_r > 0.0);
+  float* const master = e->layer[RNA_LAYER_MASTER];
+  const float* const laser = e->layer[RNA_LAYER_LASER];
   {
     KernelTimer kt(e, RNA_K_COMPOSE);
-    if (full) {
-      RNA_HIP(e, hipMemcpyAsync(e->layer[RNA_LAYER_MASTER], e->layer[RNA_LAYER_LASER], e->ncell * sizeof(float),
-                                hipMemcpyDeviceToDevice, e->stream));
+    if (plan.copy == ComposeCopy::Fused) {
+      // copy, ring refresh and flags in one launch; the two flag arrays swap roles (what this compose consumed =
+      // rna_last_dirty_tiles; the other one, cleared by the launch, is marked next)
+      static const int wgs_per_cu = [] { const char* v = getenv("RNA_COMPOSE_WGS_PER_CU"); const int n = v ? atoi(v) : 0; return n > 0 ? n : 16; }();   // developer knob
+      hipLaunchKernelGGL(compose_nbr_tiles_kernel, dim3(std::min(e->tiles_i * e->tiles_j, wgs_per_cu * e->cu_count)), dim3(256), 0, e->stream, e->nbr,
+                         master, laser, e->dirty_tiles, e->last_dirty, e->geom.size[0], e->geom.size[1], e->tiles_i, e->tiles_j);
+      RNA_HIP(e, hipGetLastError());
+      std::swap(e->dirty_tiles, e->last_dirty);
+      e->map.composed(plan);
+      return RNA_OK;
+    }
+    if (plan.copy == ComposeCopy::Whole) {
+      RNA_HIP(e, hipMemcpyAsync(master, laser, e->ncell * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
     } else {
-      hipLaunchKernelGGL(compose_dirty_tiles_kernel, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream,
-                         e->layer[RNA_LAYER_MASTER], e->layer[RNA_LAYER_LASER], e->dirty_tiles, e->geom.size[0],
-                         e->geom.size[1], e->tiles_i);
+      hipLaunchKernelGGL(compose_dirty_tiles_kernel, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream, master, laser,
+                         e->dirty_tiles, e->geom.size[0], e->geom.size[1], e->tiles_i);
       RNA_HIP(e, hipGetLastError());
     }
   }
-  if (e->laser_all_dirty || e->master_diverged || moved) {
-    // a layer was replaced wholesale: nothing is known about which masks are still valid; moved map: dirty tiles (buffer
-    // space) do not line up with mask tiles (map space) -- the masks are rebuilt before the next search (map_prepare_nbr)
-    e->nbr_all_dirty = true;
-  } else if (!e->nbr_all_dirty && e->robot_r > 0.0) {
-    // robot radius: the same tiles (a changed tile reaches r / res <= 63 cells, inside its ring) through footprint.hip
+  if (plan.masks == ComposeMasks::FootprintRefresh) {
     const int rc = footprint_refresh(e, 0);
     if (rc != RNA_OK) return rc;
-  } else if (!e->nbr_all_dirty) {
-    // masks were valid before this update: refresh only tiles that are dirty or touch a dirty tile
+  } else if (plan.masks == ComposeMasks::RingRefresh) {
     KernelTimer kt(e, RNA_K_NBRMASK);
-    hipLaunchKernelGGL(nbr_mask_tiles_kernel, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream, e->nbr,
-                       e->layer[RNA_LAYER_MASTER], e->dirty_tiles, 0, e->geom.size[0], e->geom.size[1], e->tiles_i,
-                       e->tiles_j, 0, 0);
+    hipLaunchKernelGGL(nbr_mask_tiles_kernel, dim3(e->tiles_i, e->tiles_j), dim3(256), 0, e->stream, e->nbr, master,
+                       e->dirty_tiles, 0, e->geom.size[0], e->geom.size[1], e->tiles_i, e->tiles_j, 0, 0);
     RNA_HIP(e, hipGetLastError());
-  }
+  }   // (waiting masks are rebuilt before the next search, map_prepare_nbr)
   // what this compose consumed: the tiles a tiled deployment has to hand to the other GPUs (rna_last_dirty_tiles)
-  if (full) {
-    RNA_HIP(e, hipMemsetAsync(e->last_dirty, 1, words * sizeof(unsigned), e->stream));
+  const size_t flag_bytes = flag_words(e) * sizeof(unsigned);
+  if (plan.last_dirty == ComposeLastDirty::AllOnes) {
+    RNA_HIP(e, hipMemsetAsync(e->last_dirty, 1, flag_bytes, e->stream));
   } else {
-    RNA_HIP(e, hipMemcpyAsync(e->last_dirty, e->dirty_tiles, words * sizeof(unsigned), hipMemcpyDeviceToDevice, e->stream));
+    RNA_HIP(e, hipMemcpyAsync(e->last_dirty, e->dirty_tiles, flag_bytes, hipMemcpyDeviceToDevice, e->stream));
   }
-  RNA_HIP(e, hipMemsetAsync(e->dirty_tiles, 0, words * sizeof(unsigned), e->stream));
-  e->laser_all_dirty = false;
-  e->master_diverged = false;
+  RNA_HIP(e, hipMemsetAsync(e->dirty_tiles, 0, flag_bytes, e->stream));
+  e->map.composed(plan);
   return RNA_OK;
 }
 
@@ -817,7 +782,6 @@ extern "C" int rna_compose_master(rna_engine* e, int mode) {
 extern "C" int rna_move(rna_engine* e, double nx, double ny, int* moved) {
   if (!e) return RNA_EINVAL;
   RNA_ENTER(e);
-  e->map_epoch++;
   Geom& g = e->geom;
   const double pshift[2] = {nx - g.pos[0], ny - g.pos[1]};
   int ishift[2];
@@ -827,6 +791,8 @@ extern "C" int rna_move(rna_engine* e, double nx, double ny, int* moved) {
     ishift[a] = -(int)(t + 0.5 * (t > 0 ? 1 : -1));
     aligned[a] = (double)(-ishift[a]) * g.res;
   }
+  const bool by_a_cell = ishift[0] != 0 || ishift[1] != 0;
+  e->map.moved(by_a_cell);
   auto clear = [&](int i0, int ni, int j0, int nj) -> int {
     if (ni <= 0 || nj <= 0) return RNA_OK;
     for (int l = 0; l < RNA_NUM_LAYERS; ++l) {
@@ -864,8 +830,7 @@ extern "C" int rna_move(rna_engine* e, double nx, double ny, int* moved) {
   g.start[1] = wrap_index(g.start[1] + ishift[1], g.size[1]);
   g.pos[0] += aligned[0];
   g.pos[1] += aligned[1];
-  if (ishift[0] != 0 || ishift[1] != 0) e->nbr_all_dirty = true;
-  if (moved) *moved = (ishift[0] != 0 || ishift[1] != 0);
+  if (moved) *moved = by_a_cell;
   return RNA_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include "../../include/rna.h"
 #include "gridmath.hpp"
+#include "map_state.hpp"
 
 // control words of the goal field and of the frontiers: each private to its file (defined in its unnamed namespace)
 namespace {
@@ -40,7 +41,7 @@ struct HimmScratch {
   size_t pairs_cap = 0;          // ints allocated for them
   bool pairs_checked = false;    // pairs_cap is below the worst case: every batch's pair count is read back before it is used
   int* pairs_total_host = nullptr;   // pinned: the count of the batch being launched (pairs_checked only)
-  int* tile_bins = nullptr;      // [3][ntile]: pair count, offset and fill cursor per tile
+  int* tile_bins = nullptr;      // per-tile pair counts, offsets, fill cursors and the rasteriser's job list: one block, laid out by HimmBins (himm.hip)
   int win[4] = {0, 0, 0, 0};     // owner window [i0, i1) x [j0, j1) in buffer indices; i1 == 0: whole map
 };
 
@@ -162,7 +163,7 @@ struct GoalField {
   uint8_t* touched = nullptr;      // [tiles]: the tile has been relaxed during this build
   CtlPair<GfCtl> ctl;              // control words
   int rows = 0, cols = 0, s0 = 0, s1 = 0;   // geometry the field was built with (paths are walked in its map space)
-  unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
+  unsigned long long epoch = 0;    // rna_engine::map.epoch at the build
   rna_goal_field_info info{-1, 0, 0, 0, 0, 0, 0, 0};
   // many sources (rna_goal_field_build_multi): the last build's source counts, and the owner labels when it asked for them
   rna_goal_field_sources_info sources{0, 0, 0, 0, 0, {0, 0, 0}};
@@ -180,7 +181,7 @@ struct GoalField {
 struct Clearance {
   uint16_t* clr = nullptr;         // [ncell] buffer order: di^2 + dj^2, 0 on blocked cells, RNA_CLEARANCE_NONE beyond the cap
   int R = 0;                       // cap in cells of the field that is there (0 = none)
-  unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
+  unsigned long long epoch = 0;    // rna_engine::map.epoch at the build
 };
 
 // Exploration frontiers (frontier.hip): labels of the 8-connected clusters of frontier cells and their records, built on request.
@@ -192,7 +193,7 @@ struct Frontiers {
   int rec_cap = 0;
   CtlPair<FrCtl> ctl;              // control words
   bool built = false;
-  unsigned long long epoch = 0;    // rna_engine::map_epoch at the build
+  unsigned long long epoch = 0;    // rna_engine::map.epoch at the build
   rna_frontier_info info{0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -222,10 +223,8 @@ struct rna_engine {
   unsigned* last_dirty = nullptr;    // the flags the last compose consumed (tiled mode: what this GPU has to hand on)
   int32_t* tile_list = nullptr;      // staging for rna_layer_pack_tiles / rna_layers_unpack_tiles
   int tile_list_cap = 0;
-  bool laser_all_dirty = false;      // laser uploaded/filled: next compose is a whole-layer copy
-  bool master_diverged = false;      // master written directly: next compose is a whole-layer copy
+  rna::MapState map;                 // what the next compose or search has to redo, and the epoch (map_state.hpp)
   uint8_t* nbr = nullptr;            // A* neighbour masks derived from master
-  bool nbr_all_dirty = true;
   // Robot radius of the grid A* (rna_astar_set_robot_radius, footprint.hip): 0 = point robot (the masks come from
   // nbr_mask_tiles_kernel / compose_nbr_tiles_kernel exactly as before); > 0 = the masks are built from the blocked set
   // of GlobalPlanner::ifBlocked with this radius by footprint_tiles_kernel.
@@ -234,9 +233,6 @@ struct rna_engine {
   rna::FootprintPlan fp{};           // r > 0: the disc stencil, classified for the geometry's coordinate magnitude
   int2* fp_ties = nullptr;           // r > 0: the tie offsets of fp (device)
   int fp_ties_cap = 0;
-  // counts the calls that can change the neighbour masks (map updates, compose, uploads / fills / unpacks, moves, a new
-  // robot radius): a goal field built at another count reports itself stale
-  unsigned long long map_epoch = 0;
   rna::GoalField gfield;
   rna::Clearance clearance;
   rna::Frontiers frontiers;

@@ -266,8 +266,7 @@ extern "C" int rna_astar_set_robot_radius(rna_engine* e, double radius) {
     return fail(e, RNA_EINVAL, "robot radius must satisfy 0 <= r and r / resolution <= 63");
   RNA_ENTER(e);   // joins the snapshots in flight: they read the masks the next refresh rebuilds
   e->robot_r = radius;
-  e->map_epoch++;
-  e->nbr_all_dirty = true;
+  e->map.radius_set();
   return RNA_OK;
 }
 

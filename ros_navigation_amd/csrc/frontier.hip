@@ -378,7 +378,7 @@ extern "C" int rna_frontiers_build(rna_engine* e, int min_size, unsigned flags, 
   // (argument checks first: none of them reads the engine)
   if (!e || min_size < 1 || cap < 0 || (flags & ~(unsigned)RNA_FRONTIER_RANK) || (cap > 0 && !out_host)) return RNA_EINVAL;
   const bool rank = (flags & RNA_FRONTIER_RANK) != 0;
-  if (rank && (e->gfield.info.goal < 0 || e->gfield.epoch != e->map_epoch || e->gfield.cost_changed))
+  if (rank && (e->gfield.info.goal < 0 || e->gfield.epoch != e->map.epoch || e->gfield.cost_changed))
     return fail(e, RNA_ESTATE, "rna_frontiers_build: RNA_FRONTIER_RANK needs a current goal field (rna_goal_field_build)");
   if (e->ncell > (size_t)INT_MAX) return fail(e, RNA_ECAPACITY, "rna_frontiers_build: a label is an int32, the map has 2^31 cells or more");
   RNA_ENTER(e);
@@ -419,7 +419,7 @@ extern "C" int rna_frontiers_build(rna_engine* e, int min_size, unsigned flags, 
     if (host->overflow) return fail(e, RNA_ECAPACITY, "rna_frontiers_build: a cluster root without a record");
   }
   f.info = rna_frontier_info{host->cells, roots, host->kept, host->largest, min_size, rank ? 1 : 0, 0, 0};
-  f.epoch = e->map_epoch;
+  f.epoch = e->map.epoch;
   f.built = true;
   if (info_host) *info_host = f.info;
   if (cap == 0) return RNA_OK;
@@ -438,7 +438,7 @@ extern "C" int rna_frontiers_build(rna_engine* e, int min_size, unsigned flags, 
 extern "C" int rna_frontiers_info_get(const rna_engine* e, rna_frontier_info* out) {
   if (!e || !out) return RNA_EINVAL;
   *out = e->frontiers.info;
-  out->stale = (e->frontiers.built && e->frontiers.epoch != e->map_epoch) ? 1 : 0;
+  out->stale = (e->frontiers.built && e->frontiers.epoch != e->map.epoch) ? 1 : 0;
   return RNA_OK;
 }
 

@@ -641,7 +641,7 @@ int gf_build(rna_engine* e, const int32_t* goals, const int32_t* seed, int n, in
   const bool pen = f.cost_n > 0;
   const int pen_r = f.cost_n - 1, pen_r2 = pen_r * pen_r;
   if (pen) {
-    if (e->clearance.R != pen_r || e->clearance.epoch != e->map_epoch)
+    if (e->clearance.R != pen_r || e->clearance.epoch != e->map.epoch)
       if ((rc = clearance_refresh(e, pen_r)) != RNA_OK) return rc;
     if (!f.pen_current) {
       std::vector<uint16_t> tab((size_t)pen_r2 + 1, 0);
@@ -703,7 +703,7 @@ int gf_build(rna_engine* e, const int32_t* goals, const int32_t* seed, int n, in
                      f.pen, pen_r2);
   if ((rc = f.ctl.read(e)) != RNA_OK) return rc;
   f.rows = rows; f.cols = cols; f.s0 = s0; f.s1 = s1;
-  f.epoch = e->map_epoch;
+  f.epoch = e->map.epoch;
   f.cost_changed = false;
   if (getenv("RNA_GOAL_FIELD_STATS"))   // developer knob
     fprintf(stderr, "[goal field] width %u: %d rounds, %d tile jobs on %d tiles, %d passes (longest job %d)\n", width, host->rounds,
@@ -803,7 +803,7 @@ extern "C" int rna_goal_field_owners_at(rna_engine* e, const int32_t* cells_host
 extern "C" int rna_goal_field_info_get(const rna_engine* e, rna_goal_field_info* out) {
   if (!e || !out) return RNA_EINVAL;
   *out = e->gfield.info;
-  out->stale = (out->goal >= 0 && (e->gfield.epoch != e->map_epoch || e->gfield.cost_changed)) ? 1 : 0;
+  out->stale = (out->goal >= 0 && (e->gfield.epoch != e->map.epoch || e->gfield.cost_changed)) ? 1 : 0;
   return RNA_OK;
 }
 

@@ -24,8 +24,9 @@
 // Round 5 ran the whole chain (and the compose) as the phases of ONE persistent kernel with device-wide barriers: exact, and
 // slower in the replan loop (95-130 k against 146 k cycles/s, profiles/r05_fused_map_update_*.txt) -- next to the searches every
 // phase took as long as the kernel it replaced (their time there is memory latency under load, not launch overhead), the compose
-// phase serialised the update with the side work, and a barrier whose workgroups cannot all be resident can only trap.  Removed;
-// the kernels' bodies stayed the device functions it was built from.
+// phase serialised the update with the side work, and a barrier whose workgroups cannot all be resident can only trap.  Removed.
+// himm_prep, himm_collect, himm_bin_scan and himm_tile_raster are still a kernel around the device function that was its phase:
+// as one body each compiles to other instructions (profiles/map_update_host_asm.txt).  himm_apply folds without a trace.
 // Round 1 rasterised ray by ray with a 4-byte compare-and-swap per cell straight on HBM: 295 MB of traffic for the
 // 61 MB the batch needs (rays from one origin re-touch the same lines hundreds of times).  Per tile it is at most
 // one read and one write of 16 KB.
@@ -36,7 +37,6 @@
 using namespace rna;
 
 namespace {
-
 
 __device__ __forceinline__ float himm_clear(float v) {  // map_updater.h:61-71
   if (v <= 0.0f || v != v) v = 0.0f;
@@ -99,25 +99,22 @@ __global__ void himm_init_slots_kernel(HimmSlot* __restrict__ slots, int n_slots
   if (i == 0) *total = 0;
 }
 
-// one ray: clipping, cell count, mark registration; returns the cell count and leaves the clipped ends in `d`
-__device__ __forceinline__ int himm_prep_ray(const Geom& g, const rna_ray* __restrict__ rays, int r, int4* __restrict__ desc,
-                                             int* __restrict__ ncells, int* __restrict__ next, HimmSlot* __restrict__ slots,
-                                             int slot_mask, unsigned* __restrict__ mark_bitmap, int4 win, int4& d) {
+// one ray: clipping, cell count, mark registration
+__device__ __forceinline__ void himm_prep_ray(const Geom& g, const rna_ray* __restrict__ rays, int r, int4* __restrict__ desc, int* __restrict__ ncells,
+                                              int* __restrict__ next, HimmSlot* __restrict__ slots, int slot_mask, unsigned* __restrict__ mark_bitmap, int4 win) {
   const rna_ray ray = rays[r];
   int s[2], t[2];
   int nc = 0;
-  d = make_int4(0, 0, 0, 0);
   if (!ray_well_formed(g, ray)) {
     ncells[r] = 0;
     next[r] = -1;
-    return 0;
+    return;
   }
   if (index_limited_to_map(g, ray.sx, ray.sy, ray.ex, ray.ey, s) &&
       index_limited_to_map(g, ray.ex, ray.ey, ray.sx, ray.sy, t)) {
     const int dx = abs(t[0] - s[0]), dy = abs(t[1] - s[1]);
     nc = (dx >= dy ? dx : dy) + 1;
-    d = make_int4(s[0], s[1], t[0], t[1]);
-    desc[r] = d;
+    desc[r] = make_int4(s[0], s[1], t[0], t[1]);
   }
   ncells[r] = nc;
   next[r] = -1;
@@ -137,16 +134,13 @@ __device__ __forceinline__ int himm_prep_ray(const Geom& g, const rna_ray* __res
       atomicOr(&mark_bitmap[cell >> 5], 1u << (cell & 31));
     }
   }
-  return nc;
 }
 
-__global__ void himm_prep_kernel(Geom g, const rna_ray* __restrict__ rays, int n, int4* __restrict__ desc,
-                                 int* __restrict__ ncells, int* __restrict__ next, HimmSlot* __restrict__ slots,
-                                 int slot_mask, unsigned* __restrict__ mark_bitmap, int4 win) {
+__global__ void himm_prep_kernel(Geom g, const rna_ray* __restrict__ rays, int n, int4* __restrict__ desc, int* __restrict__ ncells,
+                                 int* __restrict__ next, HimmSlot* __restrict__ slots, int slot_mask, unsigned* __restrict__ mark_bitmap, int4 win) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
-  int4 d;
-  (void)himm_prep_ray(g, rays, r, desc, ncells, next, slots, slot_mask, mark_bitmap, win, d);
+  himm_prep_ray(g, rays, r, desc, ncells, next, slots, slot_mask, mark_bitmap, win);
 }
 
 __device__ void sift_down(int* a, int start, int end) {
@@ -162,9 +156,8 @@ __device__ void sift_down(int* a, int start, int end) {
 
 // one hash slot per thread, a workgroup's worth of slots at a time (all threads of the workgroup call: three barriers inside);
 // s_wave: one int per wavefront of the workgroup, s_base: one int
-__device__ __forceinline__ void himm_collect_slot(int h, HimmSlot* __restrict__ slots, int n_slots, const int* __restrict__ next,
-                                                  int* __restrict__ seqs, unsigned* __restrict__ before,
-                                                  unsigned* __restrict__ after, int* __restrict__ total, int* s_wave, int* s_base) {
+__device__ __forceinline__ void himm_collect_slot(int h, HimmSlot* __restrict__ slots, int n_slots, const int* __restrict__ next, int* __restrict__ seqs,
+                                                  unsigned* __restrict__ before, unsigned* __restrict__ after, int* __restrict__ total, int* s_wave, int* s_base) {
   HimmSlot sl = h < n_slots ? slots[h] : HimmSlot{-1, -1, 0, 0};
   const bool live = sl.cell >= 0;
   // One atomic per WORKGROUP on the shared running total: returning atomics on one L2 address take ~12 ns each, and the
@@ -211,9 +204,8 @@ __device__ __forceinline__ void himm_collect_slot(int h, HimmSlot* __restrict__ 
   for (int i = 0; i < len; ++i) { before[off + i] = 0; after[off + i] = 0; }
 }
 
-__global__ void __launch_bounds__(1024) himm_collect_kernel(HimmSlot* __restrict__ slots, int n_slots, const int* __restrict__ next,
-                                    int* __restrict__ seqs, unsigned* __restrict__ before,
-                                    unsigned* __restrict__ after, int* __restrict__ total) {
+__global__ void __launch_bounds__(1024) himm_collect_kernel(HimmSlot* __restrict__ slots, int n_slots, const int* __restrict__ next, int* __restrict__ seqs,
+                                                            unsigned* __restrict__ before, unsigned* __restrict__ after, int* __restrict__ total) {
   __shared__ int s_wave[16];
   __shared__ int s_base;
   himm_collect_slot(blockIdx.x * blockDim.x + threadIdx.x, slots, n_slots, next, seqs, before, after, total, s_wave, &s_base);
@@ -294,10 +286,11 @@ __global__ void himm_bin_count_kernel(const int4* __restrict__ desc, const int* 
 // list of the tiles that hold at least one ray: the rasteriser's workgroups take (tile, half) jobs from that list with a
 // ticket instead of one workgroup per half tile of the map -- of the 8192 half tiles of a 4096^2 map a 100 k-ray batch
 // touches ~1500, and next to the search workgroups that fill every CU each EMPTY workgroup still had to wait for a slot.
-template <int NT>   // threads of the (one) workgroup that runs it; LDS: three arrays of NT ints
+constexpr int HIMM_SCAN_THREADS = 1024;   // threads of the (one) workgroup that runs the scan; LDS: three arrays of as many ints
 __device__ __forceinline__ void himm_bin_scan(int* __restrict__ tile_count, int ntile, int* __restrict__ tile_off,
                                               int* __restrict__ tile_cursor, int4* __restrict__ active,
                                               int* __restrict__ n_active, int* __restrict__ ticket, int* s_part, int* s_act, int* s_act2) {
+  constexpr int NT = HIMM_SCAN_THREADS;
   // s_act: tiles with many rays -- their jobs go first (the longest jobs must not be the last ones started); s_act2: the other tiles with rays
   constexpr int HEAVY = 512;     // rays: more than one round of a rasteriser workgroup
   const int per = (ntile + NT - 1) / NT;
@@ -330,13 +323,11 @@ __device__ __forceinline__ void himm_bin_scan(int* __restrict__ tile_count, int 
   if (threadIdx.x == NT - 1) { tile_off[ntile] = s_part[NT - 1]; *n_active = s_act[NT - 1] + s_act2[NT - 1]; *ticket = 0; }
 }
 
-__global__ void __launch_bounds__(1024) himm_bin_scan_kernel(int* __restrict__ tile_count, int ntile, int* __restrict__ tile_off,
-                                                             int* __restrict__ tile_cursor, int4* __restrict__ active,
-                                                             int* __restrict__ n_active, int* __restrict__ ticket) {
-  __shared__ int s_part[1024];
-  __shared__ int s_act[1024];
-  __shared__ int s_act2[1024];
-  himm_bin_scan<1024>(tile_count, ntile, tile_off, tile_cursor, active, n_active, ticket, s_part, s_act, s_act2);
+__global__ void __launch_bounds__(HIMM_SCAN_THREADS)
+himm_bin_scan_kernel(int* __restrict__ tile_count, int ntile, int* __restrict__ tile_off, int* __restrict__ tile_cursor, int4* __restrict__ active,
+                     int* __restrict__ n_active, int* __restrict__ ticket) {
+  __shared__ int s_part[HIMM_SCAN_THREADS], s_act[HIMM_SCAN_THREADS], s_act2[HIMM_SCAN_THREADS];
+  himm_bin_scan(tile_count, ntile, tile_off, tile_cursor, active, n_active, ticket, s_part, s_act, s_act2);
 }
 
 __global__ void himm_bin_fill_kernel(const int4* __restrict__ desc, const int* __restrict__ ncells, int n, int tiles_i,
@@ -377,9 +368,8 @@ __device__ unsigned long long g_himm_stat[16];
 // a workgroup barrier that orders LDS only: global loads that are in flight stay in flight (himm_tile_raster_kernel)
 __device__ __forceinline__ void himm_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__device__ __forceinline__ void himm_count_marked_clear(int cell, int r, const HimmSlot* __restrict__ slots, int slot_mask,
-                                                        const int* __restrict__ seqs, unsigned* __restrict__ before,
-                                                        unsigned* __restrict__ after) {
+__device__ __forceinline__ void himm_count_marked_clear(int cell, int r, const HimmSlot* __restrict__ slots, int slot_mask, const int* __restrict__ seqs,
+                                                        unsigned* __restrict__ before, unsigned* __restrict__ after) {
   // count this clear in the interval before the first mark with seq >= r
   unsigned h = hash_cell((unsigned)cell) & (unsigned)slot_mask;
   while (slots[h].cell != cell) h = (h + 1) & (unsigned)slot_mask;
@@ -393,14 +383,8 @@ __device__ __forceinline__ void himm_count_marked_clear(int cell, int r, const H
   else atomicAdd(&after[off + len - 1], 1u);
 }
 
-#ifndef RNA_HIMM_TR_ROWS
-#define RNA_HIMM_TR_ROWS 32   // rows (j) of a 64 x 64 tile per job: 32 = half-tile jobs (8 KB of counters), 64 = whole tiles (16 KB)
-#endif
-constexpr int HIMM_TR_ROWS = RNA_HIMM_TR_ROWS;
-#ifndef RNA_HIMM_TR_THREADS
-#define RNA_HIMM_TR_THREADS 512
-#endif
-constexpr int HIMM_TR_THREADS = RNA_HIMM_TR_THREADS;   // (a power of two: the lane -> ray permutation of the rasteriser relies on it) // 8 wavefronts: two per SIMD next to the four of a resident search workgroup
+constexpr int HIMM_TR_ROWS = 32;       // rows (j) of a 64 x 64 tile per job: half-tile jobs, 8 KB of counters
+constexpr int HIMM_TR_THREADS = 512;   // 8 wavefronts: two per SIMD next to the four of a resident search workgroup (a power of two: the lane -> ray permutation relies on it)
 // LDS of a rasteriser workgroup
 struct RasterLds {
   unsigned cnt[HIMM_TR_ROWS * 64];   // clears per cell of this job's rows, index (j - j0) * 64 + (i & 63)
@@ -415,16 +399,12 @@ struct RasterLds {
 
 // the (tile, half) jobs of a batch, taken by the calling workgroup (HIMM_TR_THREADS threads): `first_job` first, then by
 // ticket (`grid` = workgroups that take part)
-__device__ __forceinline__ void himm_raster_jobs(RasterLds& L, const int first_job, const int grid, int rows, int cols, int tiles_i, const int4* __restrict__ desc,
-                                                               const int* __restrict__ ncells,
-                                                               const int* __restrict__ tile_off, const int* __restrict__ pairs,
-                                                               const int4* __restrict__ active, const int* __restrict__ n_active,
-                                                               int* __restrict__ ticket,
-                                                               float* __restrict__ layer, const unsigned* __restrict__ mark_bitmap,
-                                                               const HimmSlot* __restrict__ slots, int slot_mask,
-                                                               const int* __restrict__ seqs, unsigned* __restrict__ before,
-                                                               unsigned* __restrict__ after, unsigned* __restrict__ dirty_tiles, int4 win) {
-
+__device__ __forceinline__ void himm_raster_jobs(RasterLds& L, const int first_job, const int grid, int rows, int cols, int tiles_i,
+                                                 const int4* __restrict__ desc, const int* __restrict__ ncells, const int* __restrict__ tile_off,
+                                                 const int* __restrict__ pairs, const int4* __restrict__ active, const int* __restrict__ n_active,
+                                                 int* __restrict__ ticket, float* __restrict__ layer, const unsigned* __restrict__ mark_bitmap,
+                                                 const HimmSlot* __restrict__ slots, int slot_mask, const int* __restrict__ seqs,
+                                                 unsigned* __restrict__ before, unsigned* __restrict__ after, unsigned* __restrict__ dirty_tiles, int4 win) {
   constexpr int JPT = 64 / HIMM_TR_ROWS, NW = HIMM_TR_ROWS * 2;   // jobs per 64 x 64 tile; words of mark bits per job
   const int njobs = JPT * *n_active;
   // Which ray of a round a lane takes (-1: none).  A round is up to HIMM_TR_THREADS rays; a shorter one is dealt to the
@@ -645,25 +625,21 @@ __device__ __forceinline__ void himm_raster_jobs(RasterLds& L, const int first_j
   }   // next job
 }
 
-__global__ void __launch_bounds__(HIMM_TR_THREADS) himm_tile_raster_kernel(int rows, int cols, int tiles_i, const int4* __restrict__ desc,
-                                                               const int* __restrict__ ncells,
-                                                               const int* __restrict__ tile_off, const int* __restrict__ pairs,
-                                                               const int4* __restrict__ active, const int* __restrict__ n_active,
-                                                               int* __restrict__ ticket,
-                                                               float* __restrict__ layer, const unsigned* __restrict__ mark_bitmap,
-                                                               const HimmSlot* __restrict__ slots, int slot_mask,
-                                                               const int* __restrict__ seqs, unsigned* __restrict__ before,
-                                                               unsigned* __restrict__ after, unsigned* __restrict__ dirty_tiles, int4 win) {
+__global__ void __launch_bounds__(HIMM_TR_THREADS)
+himm_tile_raster_kernel(int rows, int cols, int tiles_i, const int4* __restrict__ desc, const int* __restrict__ ncells, const int* __restrict__ tile_off,
+                        const int* __restrict__ pairs, const int4* __restrict__ active, const int* __restrict__ n_active, int* __restrict__ ticket,
+                        float* __restrict__ layer, const unsigned* __restrict__ mark_bitmap, const HimmSlot* __restrict__ slots, int slot_mask,
+                        const int* __restrict__ seqs, unsigned* __restrict__ before, unsigned* __restrict__ after, unsigned* __restrict__ dirty_tiles, int4 win) {
   __shared__ RasterLds L;
   himm_raster_jobs(L, (int)blockIdx.x, (int)gridDim.x, rows, cols, tiles_i, desc, ncells, tile_off, pairs, active, n_active, ticket, layer, mark_bitmap,
                    slots, slot_mask, seqs, before, after, dirty_tiles, win);
 }
 
-// one hash slot: the ordered replay on its marked cell; leaves bitmap and table empty for the next batch
-__device__ __forceinline__ void himm_apply_slot(int h, int rows, HimmSlot* __restrict__ slots, int n_slots, int* __restrict__ total,
-                                                const unsigned* __restrict__ before, const unsigned* __restrict__ after,
-                                                float* __restrict__ layer, unsigned* __restrict__ mark_bitmap,
-                                                unsigned* __restrict__ dirty_tiles, int tiles_i) {
+// one hash slot per thread: the ordered replay on its marked cell; leaves bitmap and table empty for the next batch
+__global__ void himm_apply_kernel(int rows, HimmSlot* __restrict__ slots, int n_slots, int* __restrict__ total, const unsigned* __restrict__ before,
+                                  const unsigned* __restrict__ after, float* __restrict__ layer, unsigned* __restrict__ mark_bitmap,
+                                  unsigned* __restrict__ dirty_tiles, int tiles_i) {
+  const int h = blockIdx.x * blockDim.x + threadIdx.x;
   if (h == 0) *total = 0;   // (himm_collect, the only user, has finished)
   if (h >= n_slots) return;
   const HimmSlot sl = slots[h];
@@ -683,14 +659,6 @@ __device__ __forceinline__ void himm_apply_slot(int h, int rows, HimmSlot* __res
   if (dirty_tiles && reinterpret_cast<volatile unsigned char*>(dirty_tiles)[tile] != 1) reinterpret_cast<volatile unsigned char*>(dirty_tiles)[tile] = 1;
 }
 
-__global__ void himm_apply_kernel(int rows, HimmSlot* __restrict__ slots, int n_slots, int* __restrict__ total,
-                                  const unsigned* __restrict__ before, const unsigned* __restrict__ after,
-                                  float* __restrict__ layer, unsigned* __restrict__ mark_bitmap,
-                                  unsigned* __restrict__ dirty_tiles, int tiles_i) {
-  himm_apply_slot(blockIdx.x * blockDim.x + threadIdx.x, rows, slots, n_slots, total, before, after, layer, mark_bitmap, dirty_tiles, tiles_i);
-}
-
-
 // (tile, ray) pairs of a batch.  Worst case: a ray is registered with at most two tiles per 64-cell tile column it crosses,
 // i.e. 2 * ceil(max(rows, cols) / 64) + 2 pairs -- 130 ints per ray on a 4096^2 map although the bench's rays make 2.3.
 // While that is small (<= 256 MB) it is simply allocated: nothing to check, nothing to wait for.  Beyond (a million
@@ -708,9 +676,15 @@ static size_t himm_pairs_initial(const rna_engine* e, size_t cap_rays, bool* che
   return *checked ? std::min(worst, std::max(cap_rays * 16, limit / 4)) : worst;
 }
 
-// tile_bins: count [ntile] | offset [ntile + 1] | cursor [ntile] | number of tiles with rays | ticket | (16-byte aligned)
-// job records of the tiles with rays, int4 [ntile]
-static size_t himm_bins_active_at(size_t ntile) { return (3 * ntile + 3 + 3) & ~(size_t)3; }
+// HimmScratch::tile_bins, in ints from its start: pair count [ntile] | offset [ntile + 1] | fill cursor [ntile] | number of tiles
+// with rays | the rasteriser's ticket | pad to 16 bytes | job records of the tiles with rays, int4 [ntile].  The counts are all
+// zero between batches (the scan leaves them so).
+struct HimmBins {
+  size_t count, off, cursor, n_active, ticket, active, total;   // (initialised in this order)
+  explicit HimmBins(size_t ntile)
+      : count(0), off(ntile), cursor(off + ntile + 1), n_active(cursor + ntile), ticket(n_active + 1), active((ticket + 1 + 3) & ~(size_t)3),
+        total(active + 4 * ntile) {}
+};
 
 int ensure_scratch(rna_engine* e, int n) {
   HimmScratch& s = e->himm;
@@ -720,9 +694,7 @@ int ensure_scratch(rna_engine* e, int n) {
     if ((rc = dev_alloc(e, &s.mark_bitmap, words)) != RNA_OK) return rc;
     RNA_HIP(e, hipMemsetAsync(s.mark_bitmap, 0, words * sizeof(unsigned), e->stream));
     if ((rc = dev_alloc(e, &s.total, 1)) != RNA_OK) return rc;
-    // per 64 x 64 tile: count | offset (ntile + 1) | cursor | list of the tiles with rays, then their number and the
-    // rasteriser's ticket; the counts are all zero between batches (the scan leaves them so)
-    const size_t bins = himm_bins_active_at((size_t)e->tiles_i * e->tiles_j) + (size_t)4 * e->tiles_i * e->tiles_j;
+    const size_t bins = HimmBins((size_t)e->tiles_i * e->tiles_j).total;
     if ((rc = dev_alloc(e, &s.tile_bins, bins)) != RNA_OK) return rc;
     RNA_HIP(e, hipMemsetAsync(s.tile_bins, 0, bins * sizeof(int), e->stream));
   }
@@ -733,17 +705,18 @@ int ensure_scratch(rna_engine* e, int n) {
   // a failed regrow leaves no half-sized scratch behind: the next call starts from nothing again
   s.cap_rays = 0;
   s.n_slots = 0;
+  const size_t pairs = himm_pairs_initial(e, (size_t)cap, &s.pairs_checked);
   if ((rc = dev_alloc(e, &s.rays_dev, (size_t)cap)) != RNA_OK || (rc = dev_alloc(e, &s.desc, (size_t)cap)) != RNA_OK ||
       (rc = dev_alloc(e, &s.ncells, (size_t)cap)) != RNA_OK || (rc = dev_alloc(e, &s.next, (size_t)cap)) != RNA_OK ||
       (rc = dev_alloc(e, &s.seqs, (size_t)cap)) != RNA_OK || (rc = dev_alloc(e, &s.before, (size_t)cap)) != RNA_OK ||
       (rc = dev_alloc(e, &s.after, (size_t)cap)) != RNA_OK || (rc = dev_alloc(e, &s.slots, (size_t)cap * 2)) != RNA_OK ||
-      (rc = dev_alloc(e, &s.pairs, himm_pairs_initial(e, (size_t)cap, &s.pairs_checked))) != RNA_OK) {
+      (rc = dev_alloc(e, &s.pairs, pairs)) != RNA_OK) {
     const std::string why = e->err;
     (void)himm_release(e);
     e->err = why;
     return rc;
   }
-  s.pairs_cap = himm_pairs_initial(e, (size_t)cap, &s.pairs_checked);
+  s.pairs_cap = pairs;
   if (s.pairs_checked && !s.pairs_total_host)
     RNA_HIP(e, hipHostMalloc(reinterpret_cast<void**>(&s.pairs_total_host), sizeof(int), hipHostMallocDefault));
   s.n_slots = cap * 2;
@@ -762,6 +735,8 @@ int himm_launch(rna_engine* e, int layer, const rna_ray* rays_dev, int n) {
   if (n_slots > s.n_slots) n_slots = s.n_slots;
   const int4 win = s.win[1] > 0 ? make_int4(s.win[0], s.win[1], s.win[2], s.win[3])
                                 : make_int4(0, g.size[0], 0, g.size[1]);
+  // flags exist for the laser layer only ("laser differs from master here")
+  unsigned* const dirty = layer == RNA_LAYER_LASER ? e->dirty_tiles : nullptr;
   {
     KernelTimer kt(e, RNA_K_HIMM_PREP);
     // (the hash table is empty and *total is 0: himm_apply leaves them so, ensure_scratch starts them so)
@@ -774,14 +749,12 @@ int himm_launch(rna_engine* e, int layer, const rna_ray* rays_dev, int n) {
   {
     KernelTimer kt(e, RNA_K_HIMM_RASTER);
     const int ntile = e->tiles_i * e->tiles_j;
-    int* count = s.tile_bins;
-    int* off = s.tile_bins + ntile;
-    int* cursor = s.tile_bins + 2 * ntile + 1;
-    int* n_active = s.tile_bins + 3 * ntile + 1;
-    int* ticket = s.tile_bins + 3 * ntile + 2;
-    int4* active = reinterpret_cast<int4*>(s.tile_bins + himm_bins_active_at((size_t)ntile));
+    const HimmBins at((size_t)ntile);
+    int *count = s.tile_bins + at.count, *off = s.tile_bins + at.off, *cursor = s.tile_bins + at.cursor;
+    int *n_active = s.tile_bins + at.n_active, *ticket = s.tile_bins + at.ticket;
+    int4* active = reinterpret_cast<int4*>(s.tile_bins + at.active);
     hipLaunchKernelGGL(himm_bin_count_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, s.desc, s.ncells, n, e->tiles_i, count);
-    hipLaunchKernelGGL(himm_bin_scan_kernel, dim3(1), dim3(1024), 0, e->stream, count, ntile, off, cursor, active, n_active, ticket);
+    hipLaunchKernelGGL(himm_bin_scan_kernel, dim3(1), dim3(HIMM_SCAN_THREADS), 0, e->stream, count, ntile, off, cursor, active, n_active, ticket);
     if (s.pairs_checked) {   // the buffer is smaller than the worst case: this batch's exact pair count, before anything is written
       RNA_HIP(e, hipMemcpyAsync(s.pairs_total_host, off + ntile, sizeof(int), hipMemcpyDeviceToHost, e->stream));
       RNA_HIP(e, hipStreamSynchronize(e->stream));
@@ -801,17 +774,18 @@ int himm_launch(rna_engine* e, int layer, const rna_ray* rays_dev, int n) {
     if (const char* w = getenv("RNA_HIMM_RASTER_WGS")) raster_wgs = std::max(1, std::min((64 / HIMM_TR_ROWS) * ntile, atoi(w)));   // developer knob
     hipLaunchKernelGGL(himm_tile_raster_kernel, dim3(raster_wgs), dim3(HIMM_TR_THREADS), 0, e->stream, g.size[0], g.size[1], e->tiles_i, s.desc,
                        s.ncells, off, s.pairs, active, n_active, ticket, e->layer[layer], s.mark_bitmap, s.slots, n_slots - 1, s.seqs, s.before,
-                       s.after, layer == RNA_LAYER_LASER ? e->dirty_tiles : nullptr, win);
+                       s.after, dirty, win);
     RNA_HIP(e, hipGetLastError());
   }
   {
     KernelTimer kt(e, RNA_K_HIMM_APPLY);
     hipLaunchKernelGGL(himm_apply_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, e->stream, g.size[0], s.slots,
-                       n_slots, s.total, s.before, s.after, e->layer[layer], s.mark_bitmap, layer == RNA_LAYER_LASER ? e->dirty_tiles : nullptr, e->tiles_i);
+                       n_slots, s.total, s.before, s.after, e->layer[layer], s.mark_bitmap, dirty, e->tiles_i);
     RNA_HIP(e, hipGetLastError());
   }
-  if (layer == RNA_LAYER_MASTER) { e->nbr_all_dirty = true; e->master_diverged = true; }
-  e->map_epoch++;
+  // the laser's tiles are flagged by the kernels; any other layer has simply changed
+  if (dirty) e->map.tiles_written();
+  else e->map.layer_written(layer);
   return RNA_OK;
 }
 

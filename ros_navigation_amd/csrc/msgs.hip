@@ -92,9 +92,7 @@ extern "C" int rna_from_occupancy_grid(rna_engine* e, int layer, const int8_t* d
                        e->layer[layer]);
   const int rc = st.finish();
   if (rc != RNA_OK) return rc;
-  if (layer == RNA_LAYER_MASTER) { e->nbr_all_dirty = true; e->master_diverged = true; }
-  if (layer == RNA_LAYER_LASER) e->laser_all_dirty = true;
-  e->map_epoch++;
+  e->map.layer_written(layer);
   return RNA_OK;
 }
 

@@ -190,7 +190,7 @@ int shortcut_paths(rna_engine* e, const int32_t* paths, const rna_astar_result* 
     return fail(e, RNA_ECAPACITY, "rna_shortcut_paths: max_path_len exceeds RNA_SHORTCUT_MAX_PATH_LEN (a path is staged in LDS)");
   if (e->geom.size[0] > 65536 || e->geom.size[1] > 65536)
     return fail(e, RNA_ECAPACITY, "rna_shortcut_paths: more than 65 536 cells along an axis");
-  if (keep && (e->clearance.R == 0 || e->clearance.epoch != e->map_epoch))
+  if (keep && (e->clearance.R == 0 || e->clearance.epoch != e->map.epoch))
     return fail(e, RNA_ESTATE, "rna_shortcut_paths: RNA_SHORTCUT_KEEP_CLEARANCE needs a current clearance field (rna_clearance_build)");
   if (n == 0) return RNA_OK;
   RNA_ENTER(e);

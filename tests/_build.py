@@ -56,6 +56,7 @@ SOURCES = {
     "rate_loop_test": ("tests/cpp/rate_loop_test.cpp", "plain"),
     "id_bootstrap_test": ("tests/cpp/id_bootstrap_test.cpp", "plain"),
     "gridmath_index_test": ("tests/cpp/gridmath_index_test.cpp", "plain"),
+    "map_state_test": ("tests/cpp/map_state_test.cpp", "plain"),
     "tiled_host": ("examples/tiled_host.cpp", "rccl"),
 }
 

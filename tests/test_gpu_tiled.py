@@ -328,3 +328,81 @@ def test_gather_dirty_with_device_side_tile_lists():
         assert same_f32(e.download(R.capi.LAYER_LASER), after), rank
         assert same_f32(e.download(R.capi.LAYER_MASTER), after), rank
         e.close()
+
+
+def test_tile_pack_and_unpack_with_the_list_in_host_and_in_device_memory():
+    """rna_layer_pack_tiles / rna_layers_unpack_tiles (tile list in host memory, synchronous) and their _device forms (list in
+    device memory, asynchronous) are one function each: the same dense buffer bit for bit, the same layers, the same flags
+    for the next compose, the same bump of the map epoch; and the host form refuses a bad list or window before it writes.
+    140 x 96 cells: 3 x 2 tiles, the last column 12 cells wide, the second row 32 tall."""
+    import torch
+    import ros_navigation_amd as R
+    LASER, MASTER, RANGE = R.capi.LAYER_LASER, R.capi.LAYER_MASTER, R.capi.LAYER_RANGE
+    rows, cols, T = 140, 96, 64
+    rng = np.random.default_rng(23)
+    values = np.array([np.nan, 0, 0, 0, 10, 50, 150, 180, 7.5], np.float32)
+    laser, other = rng.choice(values, rows * cols), rng.choice(values, rows * cols)
+    window = (20, 100, 10, 70)                            # i in [20, 120), j in [10, 80): cuts tiles on both axes
+    tiles = np.array([4, 0, 5, 3], np.int32)              # 4, 3: 32 tall; 5: 12 wide as well, and wholly outside the window
+    i0, ni, j0, nj = window
+    inside = np.zeros((cols, rows), bool)
+    inside[j0:j0 + nj, i0:i0 + ni] = True
+    want_dense = np.zeros((len(tiles), T, T), np.float32)
+    listed = np.zeros((cols, rows), bool)
+    for k, t in enumerate(tiles):
+        a, b = (t % 3) * T, (t // 3) * T
+        sel = inside[b:b + T, a:a + T]
+        want_dense[k, :sel.shape[0], :sel.shape[1]][sel] = laser.reshape(cols, rows)[b:b + T, a:a + T][sel]
+        listed[b:b + T, a:a + T] = True
+    assert not (inside & listed)[:, 128:].any() and listed[:, 128:].any()
+
+    def engine(layer):
+        e = R.Engine(rows * 0.05, cols * 0.05, 0.05)
+        assert (e.rows, e.cols) == (rows, cols) and e.tile_grid() == (3, 2)
+        e.upload(LASER, layer)
+        e.compose_master(1)
+        return e
+    src_host, src_dev, dst_host, dst_dev = engine(laser), engine(laser), engine(other), engine(other)
+    dev = src_dev._torch_device()
+    tiles_dev = torch.tensor(tiles, dtype=torch.int32, device=dev)
+    dense_host = src_host.pack_tiles(LASER, tiles, window)
+    dense_dev = torch.full((len(tiles) * T * T,), -1.0, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    src_dev.pack_tiles_device(LASER, tiles_dev.data_ptr(), len(tiles), window, dense_dev.data_ptr())
+    src_dev.synchronize()
+    assert torch.equal(dense_host.view(torch.int32), dense_dev.view(torch.int32))
+    assert same_f32(dense_host.cpu().numpy().reshape(want_dense.shape), want_dense)
+
+    goal = int(np.flatnonzero(other == 0)[0])
+    for e in (dst_host, dst_dev):
+        assert e.goal_field(goal)["stale"] == 0
+    dst_host.unpack_tiles((RANGE,), tiles, window, dense_host)
+    dst_dev.unpack_tiles_device((RANGE,), tiles_dev.data_ptr(), len(tiles), window, dense_dev.data_ptr())
+    assert dst_host.goal_field_info()["stale"] == 1 and dst_dev.goal_field_info()["stale"] == 1
+    dst_host.unpack_tiles((LASER, MASTER), tiles, window, dense_host)
+    dst_dev.unpack_tiles_device((LASER, MASTER), tiles_dev.data_ptr(), len(tiles), window, dense_dev.data_ptr())
+    written = (inside & listed).reshape(-1)
+    for layer, start in ((RANGE, np.full(rows * cols, np.nan, np.float32)), (LASER, other), (MASTER, other)):
+        got = dst_host.download(layer)
+        assert same_f32(got, dst_dev.download(layer)), layer
+        assert same_f32(got, np.where(written, laser, start)), layer
+    for e in (dst_host, dst_dev):
+        e.compose_master(0)
+    flags = dst_host.last_dirty_tiles()
+    assert np.array_equal(flags, dst_dev.last_dirty_tiles()) and np.array_equal(np.flatnonzero(flags), np.sort(tiles))
+
+    # refused by the host form with RNA_EINVAL, and nothing written: a tile index of ntile, a window that leaves the map
+    L, ptr = dst_host._L, R.capi._ptr
+    before = [dst_host.download(layer) for layer in (MASTER, LASER, RANGE)]
+    sentinel = torch.full_like(dense_dev, -1.0)
+    torch.cuda.synchronize()
+    for bad_tiles, bad_window in ((np.array([4, 6], np.int32), window), (tiles, (20, 130, 10, 70)), (tiles, (20, 100, 10, 90))):
+        a, na, b, nb = bad_window
+        assert L.rna_layer_pack_tiles(src_host.h, LASER, ptr(bad_tiles), len(bad_tiles), a, na, b, nb, sentinel.data_ptr()) == -1
+        assert L.rna_layers_unpack_tiles(dst_host.h, LASER, MASTER, ptr(bad_tiles), len(bad_tiles), a, na, b, nb, dense_host.data_ptr()) == -1
+    src_host.synchronize()
+    assert bool((sentinel == -1.0).all())
+    for layer, was in zip((MASTER, LASER, RANGE), before):
+        assert same_f32(dst_host.download(layer), was), layer
+    for e in (src_host, src_dev, dst_host, dst_dev):
+        e.close()
