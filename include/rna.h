@@ -222,7 +222,14 @@ typedef struct {
   int32_t emergency;           /* 1 when something was inside the safety distance */
 } rna_vfh_out;
 /* VFH::VFH + SetRobotRadius + Init (mc/src/vfh.cpp:53-110,237-416) for `n_robots` independent,
- * stateful VFH instances (Last_Binary_Hist, Last_Picked_Angle, last_chosen_speed, ...). */
+ * stateful VFH instances (Last_Binary_Hist, Last_Picked_Angle, last_chosen_speed, ...).
+ * Accepted: window_diameter 2..64, even or odd; sector_angle 3..360 with rint(360 / sector_angle) == 360 / sector_angle in
+ * integers (3, 4, 5, 6, 7, 8, 9, 10, 12, 15, 16, ... but not 11, 13, 14, 100 or 200), which keeps the histogram between 1
+ * and 128 sectors, and not 144..179 (two sectors that do not close the circle: the reference's valley borders wrap at 360
+ * there, in a sector that can open); max_speed 1..100000. Anything else is refused with RNA_EINVAL and the instances of the last
+ * successful call stay as they are.  Two inputs the reference leaves undefined are defined: the centre cell of an odd
+ * window, for which vfh.cpp:1018 reads laser_ranges[-2], is never occupied; a current speed above max_speed, which
+ * indexes Min_Turning_Radius past its end, takes the per-speed quantities of the masked histogram at max_speed. */
 int rna_vfh_init(rna_engine* e, const rna_vfh_params* p, int n_robots);
 int rna_vfh_reset(rna_engine* e);          /* re-Init every instance's state */
 int rna_vfh_hist_size(const rna_engine* e);

@@ -265,6 +265,11 @@ static int calculate_cells_mag(og_vfh* v, double ranges[361][2], int speed) {
   for (int x = 0; x < W; x++) {
     for (int y = 0; y < (int)ceil(W / 2.0); y++) {
       const int c = x * W + y;
+      /* An odd window keeps the centre row among these cells, and the centre cell's direction is -1 (vfh.cpp:292): the
+       * reference reads laser_ranges[-2], whatever lies in front of the caller's array.  Defined here and in the HIP
+       * tables: the robot's own cell is never occupied, as if that reading were "no return".  The reference gives the
+       * same answers when the doubles in front of its array are 5000 (tests/_oracle.py: ranges_array). */
+      if (v->Cell_Direction[c] < 0) { v->Cell_Mag[c] = 0.0; continue; }
       if ((v->Cell_Dist[c] + v->CELL_WIDTH / 2.0) > ranges[(int)rint(v->Cell_Direction[c] * 2.0)][0]) {
         if (v->Cell_Dist[c] < r && !(x == v->CENTER_X && y == v->CENTER_Y)) return 0;
         v->Cell_Mag[c] = v->Cell_Base_Mag[c];

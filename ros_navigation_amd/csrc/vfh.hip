@@ -577,7 +577,11 @@ vfh_step_kernel(VfhK K, Geom g, const float* __restrict__ master, const rna_pose
           }
           const int last = next == 0 ? H - 1 : next - 1;   // the valley's last free sector = (im - 1) of the closing step
           const int b1 = sct * SA;
-          const int b2 = last * SA;                    // (im - 1) * SA, + 360 when im == 0: the same number, H * SA == 360
+          // (im - 1) * SA, + 360 when im == 0: the same number where H * SA == 360.  Where it is not (sector angles 7, 16, 50 ...)
+          // the two would differ for a valley that ends in sector H - 1, and with three sectors or more there is none: the masked
+          // histogram blocks every sector behind the robot (tests/_vfh_cases.py; the sets sa7, sa16, sa50 of
+          // tests/test_gpu_vfh_params.py).  build_tables refuses the sector angles with two sectors that leave a rest.
+          const int b2 = last * SA;
           const float angle = k_delta_angle((float)b1, (float)b2);
           if (fabsf(angle) < 10) continue;
           int pos = sct - start;                 // the walk reaches this valley after `pos` steps
@@ -740,7 +744,10 @@ bool build_tables(const rna_vfh_params& p, HostTables& t) {
   t.T = (SD0 == SD1) ? 1 : 20;  // vfh.cpp:100-109
   t.CX = t.CY = (int)floor(W / 2.0);
   t.H = (int)rint(360.0 / SA);
-  if (t.H > MAX_H || t.H != 360 / SA) return false;
+  if (t.H < 1 || t.H > MAX_H || t.H != 360 / SA) return false;   // (H 0: a sector angle of 720 and more rounds to no sector at all)
+  // Two sectors that do not close the circle (sector angles 144..179): the second one, at SA degrees, can open, a valley can
+  // end in it, and the reference then closes that valley at -SA + 360 where the kernel's `last * SA` says SA (Select_Direction).
+  if (t.H == 2 && SA != 180) return false;
   t.YH = (int)ceil(W / 2.0);
   t.NQ = (t.YH + 1) * W;
   t.NQF = t.YH * W;
@@ -786,9 +793,15 @@ bool build_tables(const rna_vfh_params& p, HostTables& t) {
       t.cell_dist[q] = dist;
       t.cell_base_mag[q] = base;
       t.cell_dir[q] = d;
-      if (y < t.YH) {
+      if (y < t.YH && d < 0) {
+        // The centre cell of an odd window (direction -1) is a front cell: the reference reads laser_ranges[-2] for it, memory
+        // in front of the caller's scan.  Defined here as in oracle/vfh.c: the robot's own cell is never occupied -- a base
+        // magnitude of zero leaves its magnitude zero whatever bin it reads.
+        t.cell_base_mag[q] = 0.f;
+        t.range_idx[q] = 0;
+      } else if (y < t.YH) {
         const int ri = (int)rint(d * 2.0);  // vfh.cpp:1018
-        if (ri < 0 || ri > 360) return false;  // cannot happen for front cells (y < CY or odd-W centre row)
+        if (ri < 0 || ri > 360) return false;  // cannot happen for front cells (y < CY, or y == CY beside the centre of an odd window)
         t.range_idx[q] = ri;
       }
       for (int tb = 0; tb < T; tb++) {

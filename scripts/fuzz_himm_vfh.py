@@ -1,6 +1,7 @@
 """Developer tool: time-boxed random parity run of the map-update and VFH+ kernels against the CPU oracle: random
 geometry (size, resolution, map position, moved buffer), random layers, ray batches with end points snapped to cell
-centres / cell edges / the map border, then compose + VFH+ steps for poses anywhere (also near and past the border).
+centres / cell edges / the map border, then compose + VFH+ steps for poses anywhere (also near and past the border), for half
+of the cases at a VFH parameter set drawn from tests/_vfh_cases.py instead of the Steerer's defaults.
 Layer contents, chosen speed / turn rate, both histograms and the picked angle must agree bit for bit.
 usage: python scripts/fuzz_himm_vfh.py [seconds] [seed]"""
 import ctypes as C
@@ -16,6 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 import ros_navigation_amd as R  # noqa: E402
 import _oracle as O  # noqa: E402
+import _vfh_cases as V  # noqa: E402
 from _gpu import bits, same_f32  # noqa: E402
 
 
@@ -94,8 +96,14 @@ def main():
         poses["goal_direction"] = rng.uniform(0, 360, np_)
         poses["goal_distance"] = rng.choice([3000.0, 100.0, 800.0], np_)
         poses["goal_tolerance"] = 250.0
-        e.vfh_init(np_)
-        oracles = [O.OracleVfh(None) for _ in range(np_)]
+        vp = None                                  # the Steerer's own parameters, or one of the named sets
+        if rng.random() < 0.5:
+            here["vfh_set"] = str(rng.choice(V.NAMES))
+            vp = V.params(here["vfh_set"])
+            np_ = min(np_, 12)                     # (an oracle instance of the large sets allocates tens of megabytes)
+            poses = poses[:np_]
+        e.vfh_init(np_, V.capi_params(R, vp) if vp else None)
+        oracles = [O.OracleVfh(vp) for _ in range(np_)]
         for s in range(2):
             out, origin, hist = e.vfh_step(poses)
             for k in range(np_):

@@ -356,11 +356,13 @@ def ranges_from_submap(g, master, x, y, yaw):
 
 
 def ranges_array(vals):
-    r = Ranges()
-    for i in range(361):
-        r[i][0] = float(vals[i])
-        r[i][1] = 0.0
-    return r
+    """the 361 x 2 scan of Update_VFH, with two more pairs of 5000.0 in front of it: for the centre cell of an odd window the
+    reference reads laser_ranges[-2] (vfh.cpp:1018, Cell_Direction -1), which is then "no return" instead of whatever the
+    allocator left there (oracle/vfh.c defines that cell as never occupied and does not read it)"""
+    buf = np.full((363, 2), 5000.0)
+    buf[2:, 0] = np.asarray(vals, np.float64)[:361]
+    buf[2:, 1] = 0.0
+    return Ranges.from_buffer(buf, 32)
 
 
 class OracleVfh:

@@ -2,7 +2,8 @@
 hours) with a FIXED seed and a short budget each, as subprocesses -- random map shapes that are not multiples of the
 64 x 16 search tiles, densities 0..0.6, unknown cells, bucket widths 2828..400000, chunked batches, engine reuse, maps
 moved once or twice (grid A*); random geometry / resolution / moved buffers, end points on cell centres, edges and the
-map border, poses past the border (map update + VFH+); resolutions 0.025-0.2 m, origins up to 2000 m, radii of k and k + 1/2
+map border, poses past the border, for half of the cases one of the VFH parameter sets of tests/_vfh_cases.py
+(map update + VFH+); resolutions 0.025-0.2 m, origins up to 2000 m, radii of k and k + 1/2
 cells, moved maps (robot radius); sequences of map operations on one engine against the model of tests/_mapmodel.py (map state).
 A fuzzer exits non-zero at the first difference from the oracle
 and prints the configuration that reproduces it.  The search kernel's correctness rests on an asynchronous scheduler,
