@@ -589,6 +589,45 @@ int rna_frontiers_info_get(const rna_engine* e, rna_frontier_info* out);   /* RN
 int rna_frontiers_download(rna_engine* e, int32_t* labels_host, size_t n_cells);   /* RNA_ESTATE before a build */
 void* rna_frontiers_device_ptr(rna_engine* e);   /* int32 per cell, buffer order; NULL before a build */
 
+/* ---- global planning: information gain of view points (what a robot would learn at a frontier) ---- */
+/* The frontiers say where the known free space ends and the goal field what it costs to get there; this says what a sensor
+ * of range R cells would see from a candidate cell: exploration planners choose by utility, gain against travel cost.  Ray
+ * casting over the master layer, in map space (unwrapped indices on a moved map), integers and bit tests only: every output
+ * has exactly one right value.
+ *   unknown(c)   the master value of c is NaN
+ *   occupied(c)  the master value of c is not NaN and > 0 (GlobalPlanner::ifBlocked's predicate on the RAW layer, not the
+ *                search's blocked set: the robot radius does not stop a sensor ray)
+ *   opaque(c)    occupied(c); with RNA_VIEW_UNKNOWN_OPAQUE occupied(c) or unknown(c) -- the pessimistic gain: only what is
+ *                certainly visible
+ *   ring of v    for the view cell v = (vi, vj) and the radius R, 1 <= R <= RNA_VIEW_MAX_RADIUS: the 8R index pairs
+ *                (vi + a, vj + b) with max(|a|, |b|) = R -- raw map-space indices, they may lie outside the map
+ *   ray to e     c_0 = v, c_1 .. c_R = the cells of LineIterator(map, Index v, Index e) as rna_line_cells_index(v, e) returns
+ *                them.  The walk goes t = 1, 2, ...: it stops before c_t when c_t is outside the map or (c_t - v) has
+ *                a^2 + b^2 > R^2; otherwise c_t is seen, and if opaque(c_t) the walk stops after it
+ *   seen(v)      {v} and the seen cells of all 8R rays: a set, so it depends neither on an order nor on which thread walks
+ *                which ray
+ * One record per view point: unknown = |seen and unknown| (the gain), visible = |seen|, occupied = |seen and occupied| (the
+ * surface seen).  status 0 = evaluated: every view cell inside the map that is not occupied, an unknown one included;
+ * 1 = cell index outside [0, rows * cols); 2 = the view cell is occupied; 1 and 2 give three zeros.  View cells are buffer
+ * linear indices, like every other cell the ABI takes.  The call uses the engine's current geometry and the master layer as
+ * rna_layer_download would see it at that point of the call sequence (on the map stream, behind the map updates enqueued so
+ * far).  Not a snapshot: nothing is kept, there is no stale flag.  The _device form is asynchronous on rna_stream().
+ * RNA_EINVAL: n < 0, radius_cells < 1, unknown flag bits, NULL buffers with n > 0; RNA_ECAPACITY: radius_cells >
+ * RNA_VIEW_MAX_RADIUS (the window's three bitmaps, 24 480 B at 127, live in the LDS of one workgroup); n == 0 is RNA_OK.
+ * The record is a struct TAG (the entry point has its name): write `struct rna_view_gain`.
+ * No reference counterpart: the reference's only goal source is a click in rviz. */
+struct rna_view_gain {
+  int32_t status;        /* 0 evaluated; 1 cell out of range; 2 the view cell is occupied */
+  int32_t unknown;       /* seen cells that are unknown: the gain */
+  int32_t visible;       /* seen cells, the view cell included */
+  int32_t occupied;      /* seen cells that are occupied */
+};
+#define RNA_VIEW_UNKNOWN_OPAQUE 1
+#define RNA_VIEW_MAX_RADIUS 127
+int rna_view_gain(rna_engine* e, const int32_t* cells_host, int n, int radius_cells, unsigned flags, struct rna_view_gain* out_host);
+int rna_view_gain_device(rna_engine* e, const int32_t* cells_device, int n, int radius_cells, unsigned flags,
+                         struct rna_view_gain* out_device);
+
 /* ---- global planning: waypoint-graph A* (the reference's own AStarPlanner) ------------------- */
 /* AStarPlanner::init + makePlan over a caller-supplied graph (astar_planner.cpp:63-145): start and
  * target positions are snapped to the closest vertex; path = start, vertex locations..., target. */

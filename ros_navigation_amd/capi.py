@@ -44,6 +44,7 @@ SYMBOLS = [
     "rna_goal_field_set_clearance_cost", "rna_goal_field_get_clearance_cost",
     "rna_shortcut_paths", "rna_shortcut_paths_device", "rna_line_cells_index",
     "rna_frontiers_build", "rna_frontiers_info_get", "rna_frontiers_download", "rna_frontiers_device_ptr",
+    "rna_view_gain", "rna_view_gain_device",
     "rna_graph_astar_batch", "rna_rrt_batch", "rna_rrt_batch_device",
     "rna_to_occupancy_grid", "rna_to_occupancy_grid_device", "rna_from_occupancy_grid", "rna_vfh_hist_msg_batch",
     "rna_tailor_plan", "rna_follow_plan", "rna_get_submap", "rna_get_submap_device", "rna_create_submap", "rna_scan_to_rays", "rna_scan_to_rays_device", "rna_scan_projected_beams", "rna_range_to_rays",
@@ -77,6 +78,11 @@ class FrontierInfo(C.Structure):
     """include/rna.h rna_frontier_info (FRONTIER_INFO_DTYPE is the same record for arrays)"""
     _fields_ = [("cells", C.c_int32), ("clusters_all", C.c_int32), ("clusters", C.c_int32), ("largest", C.c_int32),
                 ("min_size", C.c_int32), ("ranked", C.c_int32), ("stale", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ViewGain(C.Structure):
+    """include/rna.h struct rna_view_gain (VIEW_GAIN_DTYPE is the same record for arrays)"""
+    _fields_ = [("status", C.c_int32), ("unknown", C.c_int32), ("visible", C.c_int32), ("occupied", C.c_int32)]
 
 
 class VfhParams(C.Structure):
@@ -130,6 +136,10 @@ FRONTIER_DTYPE = np.dtype([("label", "<i4"), ("size", "<i4"), ("min_i", "<i4"), 
 FRONTIER_INFO_DTYPE = np.dtype([("cells", "<i4"), ("clusters_all", "<i4"), ("clusters", "<i4"), ("largest", "<i4"), ("min_size", "<i4"),
                                 ("ranked", "<i4"), ("stale", "<i4"), ("reserved", "<i4")])
 FRONTIER_RANK = 1
+# include/rna.h struct rna_view_gain, the flag and the radius bound of rna_view_gain
+VIEW_GAIN_DTYPE = np.dtype([("status", "<i4"), ("unknown", "<i4"), ("visible", "<i4"), ("occupied", "<i4")])
+VIEW_UNKNOWN_OPAQUE = 1
+VIEW_MAX_RADIUS = 127
 RRT_QUERY_DTYPE = np.dtype([("start", "<f8", (2,)), ("target", "<f8", (2,)), ("close_tolerance", "<f8"),
                             ("seed", "<u4"), ("max_samples", "<i4")])
 RRT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("path_len", "<i4"), ("tree_size", "<i4"), ("samples", "<i4")])
@@ -257,6 +267,8 @@ def lib():
     L.rna_frontiers_download.argtypes = [vp, vp, C.c_size_t]
     L.rna_frontiers_device_ptr.argtypes = [vp]
     L.rna_frontiers_device_ptr.restype = vp
+    L.rna_view_gain.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint, vp]
+    L.rna_view_gain_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint, vp]
     if hasattr(L, "rna_astar_job_counters"):   # (absent only in an older build named by the developer switch RNA_LIB of bench.py's A/B runs)
         L.rna_astar_job_counters.argtypes = [vp, vp, C.c_int]
     L.rna_graph_astar_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp]
@@ -940,6 +952,28 @@ class Engine:
         info = np.zeros(1, FRONTIER_INFO_DTYPE)
         self._check(self._L.rna_frontiers_info_get(self.h, _ptr(info)))
         return self._frontier_info(info)
+
+    # ---- information gain of view points ----
+    def view_gain(self, cells, radius_cells, unknown_opaque=False):
+        """What a sensor of range radius_cells (1..VIEW_MAX_RADIUS) would see from each of `cells` (buffer linear indices), by
+        ray casting over the master layer as it is now (rna_view_gain): VIEW_GAIN_DTYPE records -- unknown (the gain),
+        visible, occupied, and status 0 evaluated / 1 cell out of range / 2 the view cell is occupied.  unknown_opaque: a ray
+        stops at the first unknown cell too (the pessimistic gain: only what is certainly visible)."""
+        cells = np.ascontiguousarray(cells, np.int32).reshape(-1)
+        out = np.zeros(len(cells), VIEW_GAIN_DTYPE)
+        self._check(self._L.rna_view_gain(self.h, _ptr(cells), len(cells), int(radius_cells), VIEW_UNKNOWN_OPAQUE if unknown_opaque else 0,
+                                          _ptr(out)))
+        return out
+
+    def view_gain_device(self, cells_ptr, n, radius_cells, out_ptr, unknown_opaque=False):
+        """the same with device pointers (n int32 cells, n 16-byte records), asynchronous on the engine's stream"""
+        self._check(self._L.rna_view_gain_device(self.h, cells_ptr, int(n), int(radius_cells), VIEW_UNKNOWN_OPAQUE if unknown_opaque else 0,
+                                                 out_ptr))
+
+    def frontier_view_gain(self, records, radius_cells, unknown_opaque=False):
+        """view_gain at the `nearest` cell of each FRONTIER_DTYPE record (Engine.frontiers): with rank=True the cell of the
+        cluster the robot reaches first, so gain and travel cost of a frontier belong to the same cell"""
+        return self.view_gain(np.asarray(records)["nearest"], radius_cells, unknown_opaque)
 
     def graph_astar(self, vertex_xy, edge_uv, start_target, edge_weight=None, max_len=None):
         v = np.ascontiguousarray(vertex_xy, dtype=np.float64).reshape(-1, 2)

@@ -653,6 +653,40 @@ inline bool findFrontiers(GridMap& map, int min_size, std::vector<Frontier>& out
   return true;
 }
 
+// Information gain of view points (rna_view_gain): what a sensor of the given range would see from a position by ray casting
+// over the master layer as it is now -- unknown = cells still NaN (the gain), visible = all cells seen, occupied = the
+// surface seen; rays stop behind the first occupied cell (the raw layer: no robot radius), with unknownOpaque behind the first
+// unknown one too.  status 0 evaluated, 2 the position's cell is occupied (three zeros).  What ranks a frontier beside its
+// travel cost: the reference has no counterpart.
+struct ViewGain { int unknown, visible, occupied, status; };
+inline bool viewGainCells(GridMap& map, const std::vector<int32_t>& cells, int radius_cells, bool unknownOpaque, std::vector<ViewGain>& out,
+                          const char* who) {
+  if (radius_cells < 1 || radius_cells > RNA_VIEW_MAX_RADIUS) return false;
+  std::vector<struct rna_view_gain> recs(cells.size());
+  grid_map::rna_check(rna_view_gain(map.engine(), cells.data(), (int)cells.size(), radius_cells, unknownOpaque ? RNA_VIEW_UNKNOWN_OPAQUE : 0u,
+                                    recs.data()), map.engine(), who);
+  out.resize(recs.size());
+  for (size_t k = 0; k < recs.size(); ++k) {
+    out[k].unknown = recs[k].unknown; out[k].visible = recs[k].visible; out[k].occupied = recs[k].occupied; out[k].status = recs[k].status;
+  }
+  return true;
+}
+// range in metres, floor(range / resolution) cells; false (and `out` untouched) for a range below one cell or beyond
+// RNA_VIEW_MAX_RADIUS cells, and for a position outside the map
+inline bool viewGain(GridMap& map, const std::vector<Position>& positions, double range, std::vector<ViewGain>& out,
+                     bool unknownOpaque = false) {
+  const double r = std::floor(range / map.getResolution());
+  if (!(r >= 1.0) || r > (double)RNA_VIEW_MAX_RADIUS) return false;
+  const int rows = map.getSize()[0];
+  std::vector<int32_t> cells(positions.size());
+  for (size_t k = 0; k < positions.size(); ++k) {
+    grid_map::Index c;
+    if (!map.getIndex(positions[k], c)) return false;
+    cells[k] = c[0] + c[1] * rows;
+  }
+  return viewGainCells(map, cells, (int)r, unknownOpaque, out, "viewGain");
+}
+
 // Grid A* over the GridMap's master layer (BASELINE.json's planner): same makePlan shape.
 static_assert(RNA_ABI_VERSION >= 6, "GridAStarPlanner's robot radius needs include/rna.h ABI version 6");
 class GridAStarPlanner {
@@ -856,6 +890,16 @@ class GridGoalField {
       return a.cost != b.cost ? a.cost < b.cost : a.label[0] + a.label[1] * rows < b.label[0] + b.label[1] * rows;
     });
     return true;
+  }
+  // ... and what the robot would learn there: viewGain at each frontier's `nearest` cell, gains[k] for frontiers[k] -- utility
+  // = gain against cost.  The map as it is NOW, not the field's snapshot; false as viewGain for the range.
+  bool frontierGains(const std::vector<Frontier>& frontiers, double range, std::vector<ViewGain>& gains) {
+    const double r = std::floor(range / map_.getResolution());
+    if (!(r >= 1.0) || r > (double)RNA_VIEW_MAX_RADIUS) return false;
+    const int rows = map_.getSize()[0];
+    std::vector<int32_t> cells(frontiers.size());
+    for (size_t k = 0; k < frontiers.size(); ++k) cells[k] = frontiers[k].nearest[0] + frontiers[k].nearest[1] * rows;
+    return viewGainCells(map_, cells, (int)r, false, gains, "GridGoalField::frontierGains");
   }
   // 1000 / 1414 integer cost from `start` to the goal; false when outside the map, unreached or beyond the 30-bit range
   bool costToGoal(Position& start, int32_t& cost) {

@@ -48,7 +48,9 @@ using core::taileredPlan;
 using core::shortcutPlan;
 using core::Frontier;
 using core::findFrontiers;
-typedef core::GridGoalField GridGoalField;   // (its frontiers() ranks them)
+using core::ViewGain;
+using core::viewGain;
+typedef core::GridGoalField GridGoalField;   // (its frontiers() ranks them, its frontierGains() says what each would show)
 
 class MapProvider;
 class Steerer;
