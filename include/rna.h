@@ -37,7 +37,7 @@ extern "C" {
  * 6, later: goal field entry points added (rna_goal_field_*, rna_goal_field_info), nothing changed -- no signature, no layout,
  *    no profile slot --, so the version stays 6.
  * 6, later still: clearance field and clearance cost (rna_clearance_*, rna_goal_field_set / _get_clearance_cost) added in the
- *    same way. */
+ *    same way.  Likewise the shortcut, the frontiers, the view gain and scan matching (rna_scan_match*). */
 #define RNA_ABI_VERSION 6
 
 typedef enum {
@@ -627,6 +627,94 @@ struct rna_view_gain {
 int rna_view_gain(rna_engine* e, const int32_t* cells_host, int n, int radius_cells, unsigned flags, struct rna_view_gain* out_host);
 int rna_view_gain_device(rna_engine* e, const int32_t* cells_device, int n, int radius_cells, unsigned flags,
                          struct rna_view_gain* out_device);
+
+/* ---- pose source: scan matching (correct a pose by correlating a scan with the map) ---------- */
+/* The map is built from whatever sensor pose the caller passes to rna_scan_to_rays; in the reference that is tf's odom ->
+ * base_link, never corrected, and HIMM writes every wall twice once odometry has drifted.  This is the correlative
+ * scan-to-map matcher that sits at that seam: before a scan is fused, search a small window of poses round the guess for
+ * the one at which the scan's end points fall on the map's occupied cells.  An exhaustive search over rotations x
+ * (2T + 1)^2 cell shifts x points, stated over integers: every output has exactly one right value.
+ * Everything is in INDEX space (index i grows as x falls, as GridMap::getIndex), cells are map-space cells (unwrapped on a
+ * moved map), and the master layer is read as rna_layer_download would see it at that point of the call sequence.
+ *   occupied(c)  c is inside the map and its master value is not NaN and > 0 (GlobalPlanner::ifBlocked's predicate on the
+ *                RAW layer: no robot radius)
+ *   bit_l(c)     l = 0 .. L - 1: some occupied cell lies within Chebyshev distance l of c.  Defined on all of Z^2: a cell
+ *                outside the map next to an occupied edge cell has bit_1.  w(c) = sum over l of bit_l(c), an integer
+ *                likelihood ramp: L on a wall, L - 1 next to it, ...  1 <= L <= RNA_SCAN_MATCH_MAX_LEVELS
+ *   points       (px, py), an int32 pair in Q6 (1/64 of a cell), sensor frame, already in index orientation.  A point is
+ *                USED iff |px|, |py| <= 32767 and px^2 + py^2 <= (64 R)^2, R = range_cells, 1 <= R <=
+ *                RNA_SCAN_MATCH_MAX_RANGE: no rotation enters, n_used is one number per query
+ *   rotation r   a pair (c, s) of int32 in Q14 supplied by the caller, n_rot of them per query (1 <= n_rot <=
+ *                RNA_SCAN_MATCH_MAX_ROT), those of query q from rot[2 * q * n_rot]:
+ *                  qx = (c * px - s * py + 8192) >> 14,  qy = (s * px + c * py + 8192) >> 14   (arithmetic shifts)
+ *                With |c|, |s| <= 16384 everything fits int32; beyond that the products wrap (no score is promised).
+ *   guess        `cell` = the buffer linear index of the cell that holds the sensor, (gi, gj) its map-space index; sub[2] =
+ *                the sensor's offset from that cell's centre in Q6, in [-32, 31].  The cell a point falls in is
+ *                  a = gi + ((qx + sub[0] + 32) >> 6),  b = gj + ((qy + sub[1] + 32) >> 6)
+ *                For a pair of magnitude 16384 (lrint(16384 cos), lrint(16384 sin)) and sub in range, |a - gi|, |b - gj| <=
+ *                R.  A used point with |a - gi| or |b - gj| > R + 1 (another pair, another sub) adds nothing to the scores
+ *                of that rotation; it still counts in n_used.
+ *   score        score(r, da, db) = sum over the used points of w((a + da, b + db)), |da|, |db| <= T = max_shift,
+ *                0 <= T <= RNA_SCAN_MATCH_MAX_SHIFT
+ *   best         compared in this order: greatest score; smallest da^2 + db^2; smallest |r - r_c|, r_c = n_rot / 2;
+ *                smallest r; smallest db; smallest da.  A total order: one value whatever the arrival order.
+ * One record per query: status 0 = matched, score = the best's, rot = its r, shift = its (da, db), n_used, score_guess =
+ * score(r_c, 0, 0), score_max = n_used * L.  status 1 = `cell` outside [0, rows * cols); status 2 = no used point; both
+ * give rot = r_c, zero shift, zero scores and n_used.  `volume`, when not NULL, receives every score as
+ * [n][n_rot][2T + 1 (db)][2T + 1 (da)] int32 (zeros for status 1 and 2): what a caller fits a covariance to.
+ * n_points <= RNA_SCAN_MATCH_MAX_POINTS per query; points_offset counts points (pairs) of the concatenated array of
+ * n_points_total points.  A query whose points leave that array: RNA_EINVAL from the host form, status 2 in the _device form.
+ * RNA_EINVAL: NULL engine, n < 0, n_rot, range_cells or levels < 1, max_shift < 0, NULL buffers with n > 0 (volume may be
+ * NULL), in the _device form records that are not 8-byte aligned; RNA_ECAPACITY (with error text): range_cells, max_shift,
+ * levels or n_rot beyond its define, or n * n_rot >= 2^24 (one workgroup each, one launch); n == 0 with valid arguments is
+ * RNA_OK.  Argument checks come before anything reads the
+ * engine.  The _device form is asynchronous on rna_stream(): three enqueues, nothing is read back; the records hold
+ * intermediate values until the last has run.  Nothing is kept: no snapshot, no device memory.
+ * The record is a struct TAG (the entry point has its name): write `struct rna_scan_match`.
+ * No reference counterpart: MapProvider never corrects the pose (gmapping is a commented-out line of a launch file). */
+struct rna_scan_match {
+  int32_t status;        /* 0 matched; 1 cell out of range; 2 no used point */
+  int32_t score;         /* the best score */
+  int32_t rot;           /* its rotation slot r */
+  int32_t shift[2];      /* its (da, db), cells in index space */
+  int32_t n_used;        /* used points */
+  int32_t score_guess;   /* score(r_c, 0, 0): what the guess itself scores */
+  int32_t score_max;     /* n_used * levels: every point on an occupied cell */
+};
+typedef struct {
+  int32_t cell;          /* buffer linear index of the cell that holds the sensor */
+  int32_t sub[2];        /* offset of the sensor from that cell's centre, Q6, [-32, 31] */
+  int32_t points_offset; /* first point of this query in the concatenated points array */
+  int32_t n_points;
+} rna_scan_match_query;
+#define RNA_SCAN_MATCH_MAX_RANGE 127
+#define RNA_SCAN_MATCH_MAX_SHIFT 16
+#define RNA_SCAN_MATCH_MAX_LEVELS 4
+#define RNA_SCAN_MATCH_MAX_ROT 128
+#define RNA_SCAN_MATCH_MAX_POINTS 8192
+int rna_scan_match(rna_engine* e, const rna_scan_match_query* queries_host, int n, const int32_t* points_host, size_t n_points_total,
+                   const int32_t* rot_host, int n_rot, int range_cells, int max_shift, int levels,
+                   struct rna_scan_match* out_host, int32_t* volume_host /* may be NULL */);
+int rna_scan_match_device(rna_engine* e, const rna_scan_match_query* queries_device, int n, const int32_t* points_device,
+                          size_t n_points_total, const int32_t* rot_device, int n_rot, int range_cells, int max_shift, int levels,
+                          struct rna_scan_match* out_device, int32_t* volume_device /* may be NULL */);
+/* Two host-only helpers, like rna_geometry_index: no engine, no GPU.
+ * rna_scan_match_prepare turns a scan's end points (sensor frame, metres, x y pairs) and a pose guess into one query:
+ *   points_q6[2k], [2k + 1] = lrint(-p / resolution * 64) (the sign is the index orientation; flipping both axes commutes
+ *                with a rotation), values beyond +-2^30 and NaN become 2^30 (never a used point);
+ *   rot_q14[2r], [2r + 1] = lrint(16384 * cos / sin(yaw + (r - r_c) * yaw_step)), r_c = n_rot / 2;
+ *   q->cell from (x, y) by the math of rna_geometry_index, q->sub = lrint(-(position - cell centre) / resolution * 64)
+ *                clamped to [-32, 31]; q->points_offset = 0, q->n_points = n_points.
+ * Returns 1; 0 when (x, y) is outside the map, with q->cell = -1 and sub 0 (points and rotations are still written);
+ * RNA_EINVAL for a bad geometry, NULL pointers, n_points < 0 or > RNA_SCAN_MATCH_MAX_POINTS, n_rot < 1 or >
+ * RNA_SCAN_MATCH_MAX_ROT.
+ * rna_scan_match_pose turns a record back into a pose: pose = (x - shift[0] * resolution, y - shift[1] * resolution,
+ * yaw + (rot - r_c) * yaw_step) -- a shift of +1 in index space lowers the coordinate by one resolution.  A record with
+ * status != 0 (rot = r_c, zero shift) returns the guess.  Returns RNA_OK or RNA_EINVAL. */
+int rna_scan_match_prepare(const rna_geometry* g, const double* points_xy, int n_points, double x, double y, double yaw, double yaw_step,
+                           int n_rot, rna_scan_match_query* q, int32_t* points_q6, int32_t* rot_q14);
+int rna_scan_match_pose(const rna_geometry* g, double x, double y, double yaw, double yaw_step, int n_rot, const struct rna_scan_match* m,
+                        double pose[3]);
 
 /* ---- global planning: waypoint-graph A* (the reference's own AStarPlanner) ------------------- */
 /* AStarPlanner::init + makePlan over a caller-supplied graph (astar_planner.cpp:63-145): start and

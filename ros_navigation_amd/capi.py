@@ -45,6 +45,7 @@ SYMBOLS = [
     "rna_shortcut_paths", "rna_shortcut_paths_device", "rna_line_cells_index",
     "rna_frontiers_build", "rna_frontiers_info_get", "rna_frontiers_download", "rna_frontiers_device_ptr",
     "rna_view_gain", "rna_view_gain_device",
+    "rna_scan_match", "rna_scan_match_device", "rna_scan_match_prepare", "rna_scan_match_pose",
     "rna_graph_astar_batch", "rna_rrt_batch", "rna_rrt_batch_device",
     "rna_to_occupancy_grid", "rna_to_occupancy_grid_device", "rna_from_occupancy_grid", "rna_vfh_hist_msg_batch",
     "rna_tailor_plan", "rna_follow_plan", "rna_get_submap", "rna_get_submap_device", "rna_create_submap", "rna_scan_to_rays", "rna_scan_to_rays_device", "rna_scan_projected_beams", "rna_range_to_rays",
@@ -83,6 +84,17 @@ class FrontierInfo(C.Structure):
 class ViewGain(C.Structure):
     """include/rna.h struct rna_view_gain (VIEW_GAIN_DTYPE is the same record for arrays)"""
     _fields_ = [("status", C.c_int32), ("unknown", C.c_int32), ("visible", C.c_int32), ("occupied", C.c_int32)]
+
+
+class ScanMatch(C.Structure):
+    """include/rna.h struct rna_scan_match (SCAN_MATCH_DTYPE is the same record for arrays)"""
+    _fields_ = [("status", C.c_int32), ("score", C.c_int32), ("rot", C.c_int32), ("shift", C.c_int32 * 2), ("n_used", C.c_int32),
+                ("score_guess", C.c_int32), ("score_max", C.c_int32)]
+
+
+class ScanMatchQuery(C.Structure):
+    """include/rna.h rna_scan_match_query (SCAN_MATCH_QUERY_DTYPE for arrays)"""
+    _fields_ = [("cell", C.c_int32), ("sub", C.c_int32 * 2), ("points_offset", C.c_int32), ("n_points", C.c_int32)]
 
 
 class VfhParams(C.Structure):
@@ -140,6 +152,15 @@ FRONTIER_RANK = 1
 VIEW_GAIN_DTYPE = np.dtype([("status", "<i4"), ("unknown", "<i4"), ("visible", "<i4"), ("occupied", "<i4")])
 VIEW_UNKNOWN_OPAQUE = 1
 VIEW_MAX_RADIUS = 127
+# include/rna.h struct rna_scan_match, rna_scan_match_query and the bounds of rna_scan_match
+SCAN_MATCH_DTYPE = np.dtype([("status", "<i4"), ("score", "<i4"), ("rot", "<i4"), ("shift", "<i4", (2,)), ("n_used", "<i4"),
+                             ("score_guess", "<i4"), ("score_max", "<i4")])
+SCAN_MATCH_QUERY_DTYPE = np.dtype([("cell", "<i4"), ("sub", "<i4", (2,)), ("points_offset", "<i4"), ("n_points", "<i4")])
+SCAN_MATCH_MAX_RANGE = 127
+SCAN_MATCH_MAX_SHIFT = 16
+SCAN_MATCH_MAX_LEVELS = 4
+SCAN_MATCH_MAX_ROT = 128
+SCAN_MATCH_MAX_POINTS = 8192
 RRT_QUERY_DTYPE = np.dtype([("start", "<f8", (2,)), ("target", "<f8", (2,)), ("close_tolerance", "<f8"),
                             ("seed", "<u4"), ("max_samples", "<i4")])
 RRT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("path_len", "<i4"), ("tree_size", "<i4"), ("samples", "<i4")])
@@ -269,6 +290,10 @@ def lib():
     L.rna_frontiers_device_ptr.restype = vp
     L.rna_view_gain.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint, vp]
     L.rna_view_gain_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint, vp]
+    L.rna_scan_match.argtypes = [vp, vp, C.c_int, vp, C.c_size_t, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.rna_scan_match_device.argtypes = L.rna_scan_match.argtypes
+    L.rna_scan_match_prepare.argtypes = [gp, vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp, vp, vp]
+    L.rna_scan_match_pose.argtypes = [gp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, vp, C.POINTER(C.c_double)]
     if hasattr(L, "rna_astar_job_counters"):   # (absent only in an older build named by the developer switch RNA_LIB of bench.py's A/B runs)
         L.rna_astar_job_counters.argtypes = [vp, vp, C.c_int]
     L.rna_graph_astar_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp]
@@ -427,6 +452,31 @@ def geometry_position(g, i, j):
     o = (C.c_double * 2)()
     rc = lib().rna_geometry_position(C.byref(g), i, j, o)
     return (o[0], o[1]) if rc == 1 else None
+
+
+def scan_match_prepare(g, points_xy, x, y, yaw, yaw_step, n_rot):
+    """rna_scan_match_prepare (host only): a scan's end points (sensor frame, metres, [n, 2]) and a pose guess -> (inside,
+    query, points_q6 [n, 2], rot_q14 [n_rot, 2]); query is a SCAN_MATCH_QUERY_DTYPE record with points_offset 0, cell -1 when
+    (x, y) is outside the map (inside False)"""
+    pts = np.ascontiguousarray(points_xy, np.float64).reshape(-1, 2)
+    q = np.zeros(1, SCAN_MATCH_QUERY_DTYPE)
+    q6 = np.zeros((len(pts), 2), np.int32)
+    rot = np.zeros((int(n_rot), 2), np.int32)
+    rc = lib().rna_scan_match_prepare(C.byref(g), _ptr(pts), len(pts), x, y, yaw, yaw_step, int(n_rot), _ptr(q), _ptr(q6), _ptr(rot))
+    if rc < 0:
+        raise RnaError("rna_scan_match_prepare failed (%s)" % STATUS.get(rc, rc))
+    return rc == 1, q[0], q6, rot
+
+
+def scan_match_pose(g, x, y, yaw, yaw_step, n_rot, record):
+    """rna_scan_match_pose (host only): the pose (x, y, yaw) a SCAN_MATCH_DTYPE record corrects the guess to"""
+    rec = np.zeros(1, SCAN_MATCH_DTYPE)
+    rec[0] = record
+    pose = (C.c_double * 3)()
+    rc = lib().rna_scan_match_pose(C.byref(g), x, y, yaw, yaw_step, int(n_rot), _ptr(rec), pose)
+    if rc != RNA_OK:
+        raise RnaError("rna_scan_match_pose failed (%s)" % STATUS.get(rc, rc))
+    return pose[0], pose[1], pose[2]
 
 
 class Engine:
@@ -974,6 +1024,63 @@ class Engine:
         """view_gain at the `nearest` cell of each FRONTIER_DTYPE record (Engine.frontiers): with rank=True the cell of the
         cluster the robot reaches first, so gain and travel cost of a frontier belong to the same cell"""
         return self.view_gain(np.asarray(records)["nearest"], radius_cells, unknown_opaque)
+
+    # ---- scan matching ----
+    def scan_match(self, queries, points, rot, range_cells, max_shift, levels, volume=False):
+        """Correct pose guesses by correlating scans with the master layer as it is now (rna_scan_match): `queries` are
+        SCAN_MATCH_QUERY_DTYPE records, `points` the concatenated [N, 2] int32 end points in Q6 cells (index orientation), `rot`
+        [n, n_rot, 2] int32 (cos, sin) pairs in Q14.  Returns SCAN_MATCH_DTYPE records; with volume=True also every score as an
+        [n, n_rot, 2 max_shift + 1 (db), 2 max_shift + 1 (da)] int32 array."""
+        queries = np.ascontiguousarray(queries, SCAN_MATCH_QUERY_DTYPE).reshape(-1)
+        points = np.ascontiguousarray(points, np.int32).reshape(-1, 2)
+        n = len(queries)
+        rot = np.ascontiguousarray(rot, np.int32).reshape(n, -1, 2) if n else np.zeros((0, 1, 2), np.int32)
+        n_rot = rot.shape[1]
+        out = np.zeros(n, SCAN_MATCH_DTYPE)
+        side = 2 * int(max_shift) + 1
+        vol = np.zeros((n, n_rot, side, side) if max_shift >= 0 else (0,), np.int32) if volume else None
+        self._check(self._L.rna_scan_match(self.h, _ptr(queries), n, _ptr(points), len(points), _ptr(rot), n_rot, int(range_cells),
+                                           int(max_shift), int(levels), _ptr(out), _ptr(vol) if volume else None))
+        return (out, vol) if volume else out
+
+    def scan_match_device(self, queries_ptr, n, points_ptr, n_points_total, rot_ptr, n_rot, range_cells, max_shift, levels, out_ptr,
+                          volume_ptr=None):
+        """the same with device pointers (n 20-byte queries, the points, n * n_rot rotation pairs, n 32-byte records, the
+        volume or None), asynchronous on the engine's stream"""
+        self._check(self._L.rna_scan_match_device(self.h, queries_ptr, int(n), points_ptr, int(n_points_total), rot_ptr, int(n_rot),
+                                                  int(range_cells), int(max_shift), int(levels), out_ptr, volume_ptr))
+
+    def scan_match_poses(self, scans, ranges, poses, yaw_step, n_rot, max_shift, levels):
+        """Scan matching from laser scans: the end points of the valid beams of each SCAN_DTYPE record (range_min <= range <=
+        range_max; at most SCAN_MATCH_MAX_POINTS, the first ones) become points through rna_scan_match_prepare with `poses`
+        [n, 3] (x, y, yaw: the sensor pose guesses; the records' own poses are not read).  The window reaches
+        floor(range / resolution) cells, range = the largest range_max of the batch -- the rule of move_control::matchScan --,
+        and as there a range below one cell or beyond SCAN_MATCH_MAX_RANGE cells is refused (RnaError: RNA_EINVAL /
+        RNA_ECAPACITY), not clamped.  Returns (records, corrected poses [n, 3]); a guess outside the map gives status 1 and
+        comes back unchanged."""
+        scans = np.ascontiguousarray(scans, SCAN_DTYPE).reshape(-1)
+        ranges = np.ascontiguousarray(ranges, np.float32).reshape(-1)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(len(scans), 3)
+        g = self.geometry()
+        queries = np.zeros(len(scans), SCAN_MATCH_QUERY_DTYPE)
+        pts, rots = [], []
+        reach = int(np.floor(float(scans["range_max"].max()) / g.resolution)) if len(scans) else 1
+        for k, s in enumerate(scans):
+            r = ranges[int(s["ranges_offset"]):int(s["ranges_offset"]) + int(s["n_ranges"])].astype(np.float64)
+            a = np.float64(s["angle_min"]) + np.arange(len(r)) * np.float64(s["angle_increment"])
+            ok = np.isfinite(r) & (r >= s["range_min"]) & (r <= s["range_max"])
+            xy = np.stack([r[ok] * np.cos(a[ok]), r[ok] * np.sin(a[ok])], axis=1)[:SCAN_MATCH_MAX_POINTS]
+            _, q, q6, rot = scan_match_prepare(g, xy, poses[k, 0], poses[k, 1], poses[k, 2], yaw_step, n_rot)
+            queries[k] = q
+            queries[k]["points_offset"] = sum(len(p) for p in pts)
+            pts.append(q6)
+            rots.append(rot)
+        points = np.concatenate(pts) if pts else np.zeros((0, 2), np.int32)
+        recs = self.scan_match(queries, points, np.stack(rots) if rots else np.zeros((0, int(n_rot), 2), np.int32),
+                               reach, max_shift, levels)
+        fixed = np.array([scan_match_pose(g, poses[k, 0], poses[k, 1], poses[k, 2], yaw_step, n_rot, recs[k]) for k in range(len(scans))],
+                         np.float64).reshape(-1, 3)
+        return recs, fixed
 
     def graph_astar(self, vertex_xy, edge_uv, start_target, edge_weight=None, max_len=None):
         v = np.ascontiguousarray(vertex_xy, dtype=np.float64).reshape(-1, 2)

@@ -149,3 +149,48 @@ extern "C" int rna_circle_cells(const rna_geometry* gg, double cx, double cy, do
   }
   return n;
 }
+
+// ---- scan matching (scanmatch.hip): a scan and a pose guess -> one query in index space, a record -> a pose ----
+extern "C" int rna_scan_match_prepare(const rna_geometry* gg, const double* points_xy, int n_points, double x, double y, double yaw,
+                                      double yaw_step, int n_rot, rna_scan_match_query* q, int32_t* points_q6, int32_t* rot_q14) {
+  if (!geom_ok(gg) || n_points < 0 || n_points > RNA_SCAN_MATCH_MAX_POINTS || n_rot < 1 || n_rot > RNA_SCAN_MATCH_MAX_ROT || !q || !rot_q14 ||
+      (n_points > 0 && (!points_xy || !points_q6)))
+    return RNA_EINVAL;
+  const Geom g = to_geom(gg);
+  for (int k = 0; k < 2 * n_points; ++k) {
+    const double v = -points_xy[k] / g.res * 64.0;
+    points_q6[k] = fabs(v) < 1073741824.0 ? (int32_t)lrint(v) : (int32_t)1073741824;   // (NaN too: never a used point)
+  }
+  const int rc = n_rot / 2;
+  for (int r = 0; r < n_rot; ++r) {
+    const double a = yaw + (double)(r - rc) * yaw_step;
+    rot_q14[2 * r] = (int32_t)lrint(16384.0 * cos(a));
+    rot_q14[2 * r + 1] = (int32_t)lrint(16384.0 * sin(a));
+  }
+  q->points_offset = 0;
+  q->n_points = n_points;
+  q->sub[0] = q->sub[1] = 0;
+  int idx[2];
+  if (!index_from_position(g, x, y, idx)) {
+    q->cell = -1;
+    return 0;
+  }
+  q->cell = idx[0] + idx[1] * g.size[0];
+  double c[2];
+  position_from_index(g, idx, c);
+  const double pos[2] = {x, y};
+  for (int a = 0; a < 2; ++a) {
+    const long s = lrint(-(pos[a] - c[a]) / g.res * 64.0);
+    q->sub[a] = (int32_t)(s < -32 ? -32 : (s > 31 ? 31 : s));
+  }
+  return 1;
+}
+
+extern "C" int rna_scan_match_pose(const rna_geometry* gg, double x, double y, double yaw, double yaw_step, int n_rot,
+                                   const struct rna_scan_match* m, double pose[3]) {
+  if (!geom_ok(gg) || n_rot < 1 || !m || !pose) return RNA_EINVAL;
+  pose[0] = x - (double)m->shift[0] * gg->resolution;
+  pose[1] = y - (double)m->shift[1] * gg->resolution;
+  pose[2] = yaw + (double)(m->rot - n_rot / 2) * yaw_step;
+  return RNA_OK;
+}

@@ -687,6 +687,80 @@ inline bool viewGain(GridMap& map, const std::vector<Position>& positions, doubl
   return viewGainCells(map, cells, (int)r, unknownOpaque, out, "viewGain");
 }
 
+// Scan matching (rna_scan_match): correct a sensor pose guess -- tf's odom -> base_link in the reference, never corrected
+// there -- by correlating the scan's end points with the occupied cells of the master layer as it is now, over a window of
+// rotations and cell shifts round the guess.  Call it between the tf lookup and LaserMapUpdater::bufferIncomingMsg.
+struct ScanMatch { int status, score, rot, shift[2], n_used, score_guess, score_max; };   // rna_scan_match's record
+// the search window: n_rot rotations yaw_step apart centred on the guess (slot n_rot / 2), shifts of up to max_shift cells
+// (0..16) in x and y, a likelihood ramp of `levels` cells (1..4) round every wall, points up to `range` metres from the sensor
+// (floor(range / resolution) cells, 1..127)
+struct ScanMatchWindow {
+  double yaw_step;
+  int n_rot, max_shift, levels;
+  double range;
+};
+struct Pose2D { double x, y, yaw; };
+// A batch: points[k] = the end points of scan k in ITS sensor frame (metres), guesses[k] the sensor pose guess in the map
+// frame.  corrected[k] = the pose the best match gives (the guess itself where records[k].status != 0: the guess outside the
+// map, no point within range); records[k].score against score_guess and score_max says how much the match is worth.  false
+// (outputs untouched) for a window outside the bounds above or more than RNA_SCAN_MATCH_MAX_POINTS points in a scan.
+inline bool matchScan(GridMap& map, const std::vector<std::vector<Position> >& points, const std::vector<Pose2D>& guesses,
+                       const ScanMatchWindow& window, std::vector<Pose2D>& corrected, std::vector<ScanMatch>& records) {
+  const rna_geometry g = map.geometry();
+  const double reach = std::floor(window.range / g.resolution);
+  if (points.size() != guesses.size() || window.n_rot < 1 || window.n_rot > RNA_SCAN_MATCH_MAX_ROT || window.max_shift < 0 ||
+      window.max_shift > RNA_SCAN_MATCH_MAX_SHIFT || window.levels < 1 || window.levels > RNA_SCAN_MATCH_MAX_LEVELS || !(reach >= 1.0) ||
+      reach > (double)RNA_SCAN_MATCH_MAX_RANGE)
+    return false;
+  const size_t n = points.size();
+  size_t total = 0;
+  for (size_t k = 0; k < n; ++k) {
+    if (points[k].size() > (size_t)RNA_SCAN_MATCH_MAX_POINTS) return false;
+    total += points[k].size();
+  }
+  std::vector<rna_scan_match_query> queries(n);
+  std::vector<int32_t> q6(2 * total + 2), rot(2 * n * (size_t)window.n_rot + 2);
+  std::vector<double> xy;
+  size_t at = 0;
+  for (size_t k = 0; k < n; ++k) {
+    xy.resize(2 * points[k].size() + 2);
+    for (size_t p = 0; p < points[k].size(); ++p) { xy[2 * p] = points[k][p].x(); xy[2 * p + 1] = points[k][p].y(); }
+    const int rc = rna_scan_match_prepare(&g, xy.data(), (int)points[k].size(), guesses[k].x, guesses[k].y, guesses[k].yaw, window.yaw_step,
+                                          window.n_rot, &queries[k], &q6[2 * at], &rot[2 * k * (size_t)window.n_rot]);
+    if (rc < 0) grid_map::rna_check(rc, nullptr, "matchScan: rna_scan_match_prepare");
+    queries[k].points_offset = (int32_t)at;
+    at += points[k].size();
+  }
+  std::vector<struct rna_scan_match> recs(n);
+  grid_map::rna_check(rna_scan_match(map.engine(), queries.data(), (int)n, q6.data(), total, rot.data(), window.n_rot, (int)reach,
+                                     window.max_shift, window.levels, recs.data(), nullptr), map.engine(), "matchScan");
+  corrected.resize(n);
+  records.resize(n);
+  for (size_t k = 0; k < n; ++k) {
+    double pose[3];
+    grid_map::rna_check(rna_scan_match_pose(&g, guesses[k].x, guesses[k].y, guesses[k].yaw, window.yaw_step, window.n_rot, &recs[k], pose),
+                        nullptr, "matchScan: rna_scan_match_pose");
+    corrected[k].x = pose[0]; corrected[k].y = pose[1]; corrected[k].yaw = pose[2];
+    ScanMatch& m = records[k];
+    m.status = recs[k].status; m.score = recs[k].score; m.rot = recs[k].rot; m.shift[0] = recs[k].shift[0]; m.shift[1] = recs[k].shift[1];
+    m.n_used = recs[k].n_used; m.score_guess = recs[k].score_guess; m.score_max = recs[k].score_max;
+  }
+  return true;
+}
+// one scan
+inline bool matchScan(GridMap& map, const std::vector<Position>& points, double guess_x, double guess_y, double guess_yaw,
+                      const ScanMatchWindow& window, Pose2D& corrected_pose, ScanMatch& record) {
+  const std::vector<std::vector<Position> > scans(1, points);
+  Pose2D guess;
+  guess.x = guess_x; guess.y = guess_y; guess.yaw = guess_yaw;
+  std::vector<Pose2D> fixed;
+  std::vector<ScanMatch> recs;
+  if (!matchScan(map, scans, std::vector<Pose2D>(1, guess), window, fixed, recs)) return false;
+  corrected_pose = fixed[0];
+  record = recs[0];
+  return true;
+}
+
 // Grid A* over the GridMap's master layer (BASELINE.json's planner): same makePlan shape.
 static_assert(RNA_ABI_VERSION >= 6, "GridAStarPlanner's robot radius needs include/rna.h ABI version 6");
 class GridAStarPlanner {

@@ -50,6 +50,10 @@ using core::Frontier;
 using core::findFrontiers;
 using core::ViewGain;
 using core::viewGain;
+using core::ScanMatch;
+using core::ScanMatchWindow;
+using core::Pose2D;
+using core::matchScan;   // (the pose source's correction: between the tf lookup and LaserMapUpdater::bufferIncomingMsg)
 typedef core::GridGoalField GridGoalField;   // (its frontiers() ranks them, its frontierGains() says what each would show)
 
 class MapProvider;
