@@ -99,9 +99,10 @@ __device__ __forceinline__ void fr_union(int32_t* lab, int a, int b, int ncell, 
 }  // namespace
 
 // One workgroup per 64 x 64 tile (MAP space; (s0, s1) = buffer start index), 256 threads:
-//  1. unknown bits of the tile's rows with one row above and below (a ballot per 64 cells of master) and of the column on
-//     either side (a ballot over the rows); free bits of the tile: known and not blocked -- the footprint's bits with a robot
-//     radius (`bits`, 64 x 64 per map-space tile), cell_blocked of master without one.  Outside the map no bit is set.
+//  1. unknown bits of the tile's rows with one row above and below (window_rows_each, a ballot per 64 cells of master) and
+//     of the column on either side (a ballot over the rows); free bits of the tile: known and not blocked -- the footprint's
+//     bits with a robot radius (`bits`, 64 x 64 per map-space tile), cell_blocked of master without one.  Outside the map
+//     no bit is set.
 //  2. frontier word of a row = free & (unknown above | below | left | right).
 //  3. node id of a cell = its tile-local index ROTATED by where the buffer wraps inside the tile (wi, wj), so that ids order
 //     like buffer indices and the smallest id of a component is its label.  Every cell starts at the smallest id of its row
@@ -121,10 +122,7 @@ __global__ void __launch_bounds__(256) fr_classify_kernel(int32_t* __restrict__ 
   const int i0 = ti * TILE, j0 = tj * TILE;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x == 0) overflow = 0;
-  for (int jj = wave; jj < TILE + 2; jj += 4) {
-    const int i = i0 + lane, j = j0 - 1 + jj;
-    const bool ok = i < rows && j >= 0 && j < cols;
-    const float v = master[ok ? buffer_lin(i, j, rows, cols, s0, s1) : 0];   // (cell 0 for lanes without a cell: read, not used)
+  window_rows_each<1>(master, i0, j0 - 1, TILE, TILE + 2, rows, cols, s0, s1, [&](int jj, int, bool ok, float v) {
     const u64 un = __ballot(ok && v != v);
     const u64 known = __ballot(ok && !(v != v));
     const u64 blk = __ballot(ok && cell_blocked(v));
@@ -132,10 +130,10 @@ __global__ void __launch_bounds__(256) fr_classify_kernel(int32_t* __restrict__ 
       unk[jj] = un;
       if (jj >= 1 && jj <= TILE) {
         const int lj = jj - 1;
-        fre[lj] = known & ~(bits ? fp_bits_word(bits, tiles_i, cols, ti, j) : blk);
+        fre[lj] = known & ~(bits ? fp_bits_word(bits, tiles_i, cols, ti, j0 + lj) : blk);
       }
     }
-  }
+  });
   if (wave < 2) {
     const int i = wave == 0 ? i0 - 1 : i0 + TILE, j = j0 + lane;
     const bool ok = i >= 0 && i < rows && j < cols;
@@ -194,8 +192,7 @@ __global__ void __launch_bounds__(256) fr_classify_kernel(int32_t* __restrict__ 
   }
 #undef FR_ID
   if (wave == 0) {
-    int n = __popcll(fr[lane]);
-    for (int o = 32; o; o >>= 1) n += __shfl_xor(n, o, 64);
+    const int n = wave_sum(__popcll(fr[lane]));
     if (lane == 0 && n) atomicAdd(&ctl->cells, n);
   }
   __syncthreads();

@@ -94,6 +94,12 @@ RNA_HD void map_cell_of(Lin lin, int rows, int cols, int s0, int s1, int& i, int
   j = buffer_to_map((int)(lin / rows), s1, cols);
 }
 
+// a buffer linear index handed in from outside is a cell of the map.  One compare: rows * cols <= 2^31 (rna_create), and a
+// negative c is at least 2^31 as an unsigned number.
+RNA_HD bool buffer_cell_in_range(int c, int rows, int cols) {
+  return (unsigned long long)(unsigned)c < (unsigned long long)rows * (unsigned long long)cols;
+}
+
 // gmc/src/GridMapMath.cpp:146-159
 RNA_HD bool position_within_map(const Geom& g, double x, double y) {
   const double tx = -((x - g.pos[0]) - 0.5 * g.len[0]);
@@ -213,6 +219,35 @@ RNA_HD int index_line_seek32(const IndexLine& l, int t, unsigned& num) {
   const unsigned c = x / (unsigned)l.D;
   num = x - c * (unsigned)l.D;
   return (int)c;
+}
+
+// The fast walk of a line with 1 <= D <= 65535: one division places the cursor at a cell, the reference's increments move it
+// on.  (The shortcut and the view-gain kernels walk a turn of 8 cells this way; tests/cpp/gridmath_index_test.cpp.)
+struct LineCursor {
+  int t, minor;   // steps taken along the major and along the minor axis
+  unsigned num;   // the walk's numerator at this cell, in [0, D)
+};
+
+RNA_HD LineCursor index_line_cursor(const IndexLine& l, int t) {   // 0 <= t <= D
+  LineCursor c;
+  c.t = t;
+  c.minor = index_line_seek32(l, t, c.num);
+  return c;
+}
+
+// the cell's offsets from the line's first cell
+RNA_HD void index_line_cursor_offset(const IndexLine& l, const LineCursor& c, int d[2]) {
+  d[0] = l.step[0] * (l.major == 0 ? c.t : c.minor);
+  d[1] = l.step[1] * (l.major == 0 ? c.minor : c.t);
+}
+
+// to the next cell; true when that step also moves along the minor axis
+RNA_HD bool index_line_cursor_step(const IndexLine& l, LineCursor& c) {
+  c.num += (unsigned)l.A;
+  const bool turn = c.num >= (unsigned)l.D;
+  if (turn) { c.num -= (unsigned)l.D; ++c.minor; }
+  ++c.t;
+  return turn;
 }
 
 // steps the minor axis has taken after t steps of the walk, 0 <= t <= D, for any D

@@ -1,8 +1,10 @@
-// map_tiles_dev.hpp -- device code shared by the kernels that work on 64 x 64 MAP-space tiles (engine.hip, footprint.hip,
-// clearance.hip, frontier.hip, goal_field.hip, shortcut.hip).  The decisions that live here and nowhere else: the blocked
-// predicate, the neighbour-mask rule and the neighbour order, the dirty ring of a tile, the occupancy bit rows of a tile in
-// LDS, and the layout of the footprint's blocked bits.  (The map <-> circular-buffer index pair is gridmath.hpp's.)
-// Everything is __forceinline__: nothing becomes a call at run time.
+// map_tiles_dev.hpp -- device code shared by the kernels that work on 64 x 64 MAP-space tiles or on a window of the master
+// layer in map space (engine.hip, footprint.hip, clearance.hip, frontier.hip, goal_field.hip, shortcut.hip, viewgain.hip,
+// scanmatch.hip).  The decisions that live here and nowhere else: the blocked predicate, the neighbour-mask rule and the
+// neighbour order, the dirty ring of a tile, the reduction over a wavefront, how a workgroup reads the rows of a window of
+// `master` (window_rows_each), the occupancy bit rows of a tile in LDS, and the layout of the footprint's blocked bits.
+// (The map <-> circular-buffer index pair, the range test of a cell handed in from outside and the line walk are
+// gridmath.hpp's.)  Everything is __forceinline__: nothing becomes a call at run time.
 #pragma once
 #include "engine.hpp"
 
@@ -98,13 +100,66 @@ __device__ __forceinline__ void compose_nbr_tile(uint8_t* __restrict__ blk, int 
   }
 }
 
+// ---- butterfly reductions over the 64 lanes of a wavefront: every lane returns the result ----
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(v, d, 64);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// ---- how a workgroup reads a window of `master`: the rows j0 .. j0 + H - 1, the columns i0 .. i0 + W - 1, W <= 64 NP, in map
+// space (the window may overhang the map on any side).  All 256 threads call.  Wavefront w takes the rows 2w, 2w + 1, then
+// + 8, ...; the 2 NP reads of a trip (2 rows x NP pieces of 64 consecutive i, through buffer_lin: coalesced, and right on a
+// moved map) leave together, before anything is done with a value.  (A read per (row, piece) and trip left the loads of a
+// wavefront one memory round trip apart.)  A lane without a cell -- its piece beyond ceil(W / 64), its column beyond W, its
+// row beyond H, or the cell outside the map -- reads nothing.  Then f(row, piece, ok, value) is called by the whole wavefront,
+// uniformly, once per (row, piece) that exists: row and piece relative to (j0, i0), ok = the lane has a cell, value = its
+// master value (0 without one).  f may ballot; what it ballots and where the bits go is the caller's. ----
+template <int NP, class F>
+__device__ __forceinline__ void window_rows_each(const float* __restrict__ master, int i0, int j0, int W, int H, int rows, int cols, int s0,
+                                                 int s1, F f) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int NC = (W + 63) >> 6;   // 64-cell pieces of a row
+  for (int r0 = 2 * wave; r0 < H; r0 += 8) {
+    float v[2][NP];
+    bool ok[2][NP];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        const int c = p * 64 + lane, i = i0 + c, j = j0 + r0 + u;
+        ok[u][p] = p < NC && r0 + u < H && c < W && i >= 0 && j >= 0 && i < rows && j < cols;
+        v[u][p] = 0.0f;
+        if (ok[u][p]) v[u][p] = master[buffer_lin(i, j, rows, cols, s0, s1)];
+      }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (r0 + u >= H) break;   // (uniform)
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        if (p >= NC) break;     // (uniform)
+        f(r0 + u, p, ok[u][p], v[u][p]);
+      }
+    }
+  }
+}
+
 // ---- occupancy bit rows of a tile in LDS: occ[row][4], row jj = map row j0 - H + jj, words 0..2 = the bits of the map cells
 // i0 - 64 .. i0 + 127, word 3 = 0 (so that a window may start anywhere in words 0..2) ----
 
 // Fills the TILE + 2 H rows of tile (i0, j0) with halo H from `master`: bit = cell_blocked, 0 outside the map and beyond the
-// halo along i.  256 threads, a wavefront per pair of rows: the six reads (3 words x 2 rows, 64 cells each) leave together,
-// then one ballot per word.  (A read per (row, word) and trip left the loads of a wavefront one memory round trip apart.)
-// The caller's barrier follows.
+// halo along i.  256 threads, the trips of window_rows_each (3 words x 2 rows), the caller's barrier follows.  NOT a caller of
+// window_rows_each, measured (profiles/window_helpers_rows_parent_vs_branch.txt): there a lane without a cell skips its read
+// under a branch of its own, here it reads cell 0 and drops it, six reads and no branch -- as a caller, with the halo clip in
+// the functor or in the window, footprint_tiles_kernel took 4 to 7 % longer (R = 3 .. 63) and clearance_tiles_kernel 2 to 9 %.
 __device__ __forceinline__ void occ_rows_load(unsigned long long (*__restrict__ occ)[4], const float* __restrict__ master, int i0, int j0,
                                               int H, int rows, int cols, int s0, int s1) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

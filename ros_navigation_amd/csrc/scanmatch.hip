@@ -64,8 +64,8 @@ __device__ __forceinline__ int sm_w(const unsigned* __restrict__ bits, int idx) 
 
 // One workgroup of 256 threads per (query, rotation); no workgroup waits for another.  Dynamic LDS only (its base stays
 // 16-byte aligned for the wide reads): the interleaved bitmaps, SM_CHUNK staged points, 16 control words.
-//  1. fill: as viewgain.hip fills its window -- a wavefront takes two window rows per turn, 64 consecutive i per load through
-//     buffer_lin (right on a moved map), one ballot per 64 cells; cells outside the map are not read and hold no bit.
+//  1. fill: the window's rows are read as map_tiles_dev.hpp's window_rows_each reads them, one ballot per 64 cells; cells
+//     outside the map hold no bit.
 //  2. dilate: level l from level l - 1, a word ORed with its two shifts (carrying across words) over its three rows.
 //  3. per chunk of SM_CHUNK points: the used ones are rotated once and staged as bit offsets ob * RB + oa (RB = bits of a
 //     bitmap row), compacted through a counter in LDS; then every thread adds w over the staged points for the <= SM_K shift
@@ -91,8 +91,7 @@ scan_match_kernel(const float* __restrict__ master, const rna_scan_match_query* 
   unsigned* const ctl = sm_lds + ((words * LS + 3) & ~3) + SM_CHUNK;
   const rna_scan_match_query qu = queries[q];
   int32_t* const vol = volume ? volume + ((size_t)q * n_rot + r) * (size_t)ncand : nullptr;
-  const unsigned long long ncell = (unsigned long long)rows * (unsigned long long)cols;   // (<= 2^31: rna_create)
-  if (qu.cell < 0 || (unsigned long long)qu.cell >= ncell) {   // (uniform) status 1: the decode kernel says so
+  if (!buffer_cell_in_range(qu.cell, rows, cols)) {   // (uniform) status 1: the decode kernel says so
     if (vol)
       for (int c = tid; c < ncand; c += SM_THREADS) vol[c] = 0;
     return;
@@ -122,32 +121,12 @@ scan_match_kernel(const float* __restrict__ master, const rna_scan_match_query* 
   }
 
   // ---- 1. the window's occupied bits: level 0 ----
-  const int NC = (W + 63) >> 6;   // 64-cell pieces of a row (<= 5)
-  for (int wb0 = 2 * wave; wb0 < W; wb0 += 8) {
-    float v[2][5];
-    bool ok[2][5];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int p = 0; p < 5; ++p) {
-        const int wa = p * 64 + lane, i = gi - H + wa, j = gj - H + wb0 + u;
-        ok[u][p] = p < NC && wb0 + u < W && wa < W && i >= 0 && j >= 0 && i < rows && j < cols;
-        v[u][p] = 0.0f;
-        if (ok[u][p]) v[u][p] = master[buffer_lin(i, j, rows, cols, s0, s1)];
-      }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (wb0 + u >= W) break;   // (uniform)
-#pragma unroll
-      for (int p = 0; p < 5; ++p) {
-        if (p >= NC) break;      // (uniform)
-        const unsigned long long mo = __ballot(ok[u][p] && cell_blocked(v[u][p]));
-        const int w = (wb0 + u) * NW + 2 * p;
-        if (lane == 0) bits[w * LS] = (unsigned)mo;
-        if (lane == 1 && 2 * p + 1 < NW) bits[(w + 1) * LS] = (unsigned)(mo >> 32);
-      }
-    }
-  }
+  window_rows_each<5>(master, gi - H, gj - H, W, W, rows, cols, s0, s1, [&](int wb, int p, bool ok, float v) {   // (W <= 295: 5 pieces)
+    const unsigned long long mo = __ballot(ok && cell_blocked(v));
+    const int w = wb * NW + 2 * p;
+    if (lane == 0) bits[w * LS] = (unsigned)mo;
+    if (lane == 1 && 2 * p + 1 < NW) bits[(w + 1) * LS] = (unsigned)(mo >> 32);
+  });
   __syncthreads();
 
   // ---- 2. the dilated levels ----
@@ -244,11 +223,7 @@ scan_match_kernel(const float* __restrict__ master, const rna_scan_match_query* 
       }
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long o = __shfl_xor(best, d, 64);
-    best = o > best ? o : best;
-  }
+  best = wave_max(best);
   unsigned long long* const wbest = reinterpret_cast<unsigned long long*>(ctl + 4);
   if (lane == 0) wbest[wave] = best;
   __syncthreads();
@@ -266,10 +241,8 @@ scan_match_decode_kernel(const rna_scan_match_query* __restrict__ queries, int n
   const int q = blockIdx.x * SM_THREADS + threadIdx.x;
   if (q >= n) return;
   const unsigned long long key = *reinterpret_cast<const unsigned long long*>(&out[q]);
-  const int32_t cell = queries[q].cell;
-  const unsigned long long ncell = (unsigned long long)rows * (unsigned long long)cols;
   ScanMatch m = {0, 0, n_rot >> 1, {0, 0}, 0, 0, 0};
-  if (cell < 0 || (unsigned long long)cell >= ncell) m.status = 1;
+  if (!buffer_cell_in_range(queries[q].cell, rows, cols)) m.status = 1;
   else if (out[q].n_used == 0) m.status = 2;
   else {
     m.score = (int32_t)(key >> 36);

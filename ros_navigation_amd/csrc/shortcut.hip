@@ -17,12 +17,6 @@ namespace {
 
 constexpr int SC_U = 8;   // line cells a lane has in flight per turn (independent loads: no address depends on a loaded value)
 
-__device__ __forceinline__ int sc_wave_sum(int v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 }  // namespace
 
 // One wavefront per path; no workgroup waits for another, no atomics.
@@ -56,13 +50,12 @@ __global__ void __launch_bounds__(64) shortcut_kernel(const int32_t* __restrict_
   }
   const int L = in.path_len;
   const int32_t* row = paths + (size_t)q * max_len;
-  const unsigned long long ncell = (unsigned long long)rows * (unsigned long long)cols;   // (<= 2^31: rna_create)
   bool bad = false;
   for (int t = lane; t < L; t += 64) {
-    unsigned c = (unsigned)row[t];
-    if ((unsigned long long)c >= ncell) { bad = true; c = 0; }
+    int32_t c = row[t];
+    if (!buffer_cell_in_range(c, rows, cols)) { bad = true; c = 0; }
     int i, j;
-    map_cell_of(c, rows, cols, s0, s1, i, j);
+    map_cell_of((unsigned)c, rows, cols, s0, s1, i, j);
     P[t] = ((unsigned)j << 16) | (unsigned)i;
   }
   __syncthreads();
@@ -81,7 +74,7 @@ __global__ void __launch_bounds__(64) shortcut_kernel(const int32_t* __restrict_
     if (lane == 0) out[q] = r;
     return;
   }
-  r.blocked_steps = sc_wave_sum(blocked);
+  r.blocked_steps = wave_sum(blocked);
 
   int32_t* wp = waypoints + (size_t)q * max_wp;
   int nw = 1, longest = 0;
@@ -129,25 +122,21 @@ __global__ void __launch_bounds__(64) shortcut_kernel(const int32_t* __restrict_
           uint8_t mask[SC_U];
           uint16_t cl[SC_U];
           unsigned bit[SC_U];
-          // one division per turn: the minor steps and the numerator at cell t, then the reference's own increments
-          unsigned num;
-          int cnt = index_line_seek32(ln, t, num);   // (act: valid, 1 <= D <= 65535)
+          // one division per turn places the cursor at cell t, then the reference's own increments
+          LineCursor cur = index_line_cursor(ln, t);   // (act: valid, 1 <= D <= 65535)
 #pragma unroll
           for (int u = 0; u < SC_U; ++u) {
-            const int tt = t + u;
-            const bool live = tt < D;   // cell tt has a step to test (cells past the line's last step read cell 0 and pass)
-            const int ci = ai + ln.step[0] * (ln.major == 0 ? tt : cnt), cj = aj + ln.step[1] * (ln.major == 0 ? cnt : tt);
-            const unsigned c = live ? buffer_lin<unsigned>(ci, cj, rows, cols, s0, s1) : 0u;
+            const bool live = cur.t < D;   // the cell has a step to test (cells past the line's last step read cell 0 and pass)
+            int d[2];
+            index_line_cursor_offset(ln, cur, d);
+            const unsigned c = live ? buffer_lin<unsigned>(ai + d[0], aj + d[1], rows, cols, s0, s1) : 0u;
             const uint8_t mk = nbr[c];
             mask[u] = live ? mk : (uint8_t)0xFF;
             if (CLR) {
               const uint16_t cv = clr[c];
               cl[u] = live ? cv : (uint16_t)RNA_CLEARANCE_NONE;
             }
-            num += (unsigned)ln.A;
-            const bool turn = num >= (unsigned)ln.D;   // the step from cell tt also moves along the minor axis
-            if (turn) { num -= (unsigned)ln.D; ++cnt; }
-            bit[u] = turn ? diagonal : straight;
+            bit[u] = index_line_cursor_step(ln, cur) ? diagonal : straight;
           }
 #pragma unroll
           for (int u = 0; u < SC_U; ++u) {

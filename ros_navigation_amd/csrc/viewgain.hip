@@ -17,13 +17,7 @@ using ViewGain = struct rna_view_gain;   // (the elaborated name: in C++ the ent
 
 namespace {
 
-constexpr int VG_U = 8;   // line cells a thread walks per division (the closed form places a turn's first cell, the reference's increments the others)
-
-__device__ __forceinline__ int vg_wave_sum(int v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
+constexpr int VG_U = 8;   // line cells a thread walks per division (gridmath.hpp's LineCursor)
 
 // words of one bitmap row and of one bitmap of the (2R + 1)^2 window
 inline int vg_row_words(int R) { return (2 * R + 1 + 31) / 32; }
@@ -34,13 +28,12 @@ inline size_t vg_lds_bytes(int R) { return (size_t)3 * (2 * R + 1) * vg_row_word
 // One workgroup of 256 threads per view point; no workgroup waits for another, no global atomics.  LDS: three bitmaps over the
 // window of W x W cells around v (W = 2R + 1), row wb = map row vj - R + wb, bit wa = map column vi - R + wa, NW 32-bit words
 // per row: occupied, unknown, seen (3 x 255 x 8 x 4 B = 24 480 B at R = 127).
-//  1. a wavefront takes two window rows per turn and reads them 64 consecutive i at a time through buffer_lin (coalesced, and
-//     right on a moved map): up to eight loads leave together, then one ballot per 64 cells and bitmap.  Cells outside the
-//     map are not read and hold no bit.  The seen bitmap starts with the bit of v alone.
+//  1. the window's rows are read as map_tiles_dev.hpp's window_rows_each reads them, one ballot per 64 cells and bitmap.
+//     Cells outside the map hold no bit.  The seen bitmap starts with the bit of v alone.
 //  2. the 8R rays are dealt to the threads: thread x takes the rays x, x + 256, ... of the list in which ray k ends at ring
 //     position (k * stride) mod 8R, gcd(stride, 8R) = 1 (a bijection; stride 1 = neighbouring lanes walk neighbouring rays,
 //     the host's other choice spreads a wavefront's lanes evenly round the ring: vg_stride below).  A thread walks in LDS only: per VG_U cells
-//     one division (index_line_seek32), then the reference's numerator increments; a seen bit is one LDS atomic OR.  The
+//     one division (index_line_cursor), then the reference's numerator increments; a seen bit is one LDS atomic OR.  The
 //     loops are bounded by R and by 8R / 256.
 //  3. popcounts of seen, seen & unknown, seen & occupied, one reduction, one 16-byte record written by thread 0.
 __global__ void __launch_bounds__(256) view_gain_kernel(const float* __restrict__ master, const int32_t* __restrict__ cells, int n, int R,
@@ -55,9 +48,8 @@ __global__ void __launch_bounds__(256) view_gain_kernel(const float* __restrict_
   unsigned* const unk = vg_bits + words;
   unsigned* const seen = vg_bits + 2 * words;
   const int32_t c = cells[q];
-  const unsigned long long ncell = (unsigned long long)rows * (unsigned long long)cols;   // (<= 2^31: rna_create)
   ViewGain r = {0, 0, 0, 0};
-  if (c < 0 || (unsigned long long)c >= ncell) r.status = 1;
+  if (!buffer_cell_in_range(c, rows, cols)) r.status = 1;
   else if (cell_blocked(master[c])) r.status = 2;
   if (r.status) {   // (uniform)
     if (tid == 0) out[q] = r;
@@ -67,33 +59,13 @@ __global__ void __launch_bounds__(256) view_gain_kernel(const float* __restrict_
   map_cell_of((unsigned)c, rows, cols, s0, s1, vi, vj);
 
   // ---- 1. the window's occupied and unknown bits ----
-  const int NC = (W + 63) >> 6;   // 64-cell pieces of a row (<= 4)
-  for (int wb0 = 2 * wave; wb0 < W; wb0 += 8) {
-    float v[2][4];
-    bool ok[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int wa = p * 64 + lane, i = vi - R + wa, j = vj - R + wb0 + u;
-        ok[u][p] = p < NC && wb0 + u < W && wa < W && i >= 0 && j >= 0 && i < rows && j < cols;
-        v[u][p] = 0.0f;
-        if (ok[u][p]) v[u][p] = master[buffer_lin(i, j, rows, cols, s0, s1)];
-      }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (wb0 + u >= W) break;   // (uniform)
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        if (p >= NC) break;      // (uniform)
-        const unsigned long long mo = __ballot(ok[u][p] && cell_blocked(v[u][p]));
-        const unsigned long long mu = __ballot(ok[u][p] && v[u][p] != v[u][p]);
-        const int w = (wb0 + u) * NW + 2 * p;
-        if (lane == 0) { occ[w] = (unsigned)mo; unk[w] = (unsigned)mu; }
-        if (lane == 1 && 2 * p + 1 < NW) { occ[w + 1] = (unsigned)(mo >> 32); unk[w + 1] = (unsigned)(mu >> 32); }
-      }
-    }
-  }
+  window_rows_each<4>(master, vi - R, vj - R, W, W, rows, cols, s0, s1, [&](int wb, int p, bool ok, float v) {   // (W <= 255: 4 pieces)
+    const unsigned long long mo = __ballot(ok && cell_blocked(v));
+    const unsigned long long mu = __ballot(ok && v != v);
+    const int w = wb * NW + 2 * p;
+    if (lane == 0) { occ[w] = (unsigned)mo; unk[w] = (unsigned)mu; }
+    if (lane == 1 && 2 * p + 1 < NW) { occ[w + 1] = (unsigned)(mo >> 32); unk[w + 1] = (unsigned)(mu >> 32); }
+  });
   const int vw = R * NW + (R >> 5);
   for (int k = tid; k < words; k += 256) seen[k] = k == vw ? 1u << (R & 31) : 0u;
   __syncthreads();
@@ -109,14 +81,13 @@ __global__ void __launch_bounds__(256) view_gain_kernel(const float* __restrict_
     const IndexLine ln = index_line(zero, end);   // (D == R: one of the two offsets has magnitude R)
     bool live = true;
     for (int t0 = 1; t0 <= R && live; t0 += VG_U) {
-      unsigned num;
-      int cnt = index_line_seek32(ln, t0, num);
+      LineCursor cur = index_line_cursor(ln, t0);
 #pragma unroll
       for (int u = 0; u < VG_U; ++u) {
-        const int t = t0 + u;
-        if (live && t <= R) {
-          const int a = ln.step[0] * (ln.major == 0 ? t : cnt), b = ln.step[1] * (ln.major == 0 ? cnt : t);
-          const int i = vi + a, j = vj + b;
+        if (live && cur.t <= R) {
+          int d[2];
+          index_line_cursor_offset(ln, cur, d);
+          const int a = d[0], b = d[1], i = vi + a, j = vj + b;
           if (i < 0 || j < 0 || i >= rows || j >= cols || a * a + b * b > RR) {
             live = false;   // the walk stops before this cell
           } else {
@@ -127,8 +98,7 @@ __global__ void __launch_bounds__(256) view_gain_kernel(const float* __restrict_
             if (stop & bit) live = false;   // ... and after this one
           }
         }
-        num += (unsigned)ln.A;
-        if (num >= (unsigned)ln.D) { num -= (unsigned)ln.D; ++cnt; }
+        index_line_cursor_step(ln, cur);
       }
     }
   }
@@ -142,9 +112,9 @@ __global__ void __launch_bounds__(256) view_gain_kernel(const float* __restrict_
     gain += __popc(s & unk[k]);
     surface += __popc(s & occ[k]);
   }
-  visible = vg_wave_sum(visible);
-  gain = vg_wave_sum(gain);
-  surface = vg_wave_sum(surface);
+  visible = wave_sum(visible);
+  gain = wave_sum(gain);
+  surface = wave_sum(surface);
   if (lane == 0) { vg_part[wave][0] = visible; vg_part[wave][1] = gain; vg_part[wave][2] = surface; }
   __syncthreads();
   if (tid == 0) {

@@ -247,6 +247,16 @@ def line_cells(g, s, e, reference=False):
     return _cells(fn, C.byref(g), d2(*s), d2(*e))
 
 
+def line_cells_index(a, b):
+    """LineIterator(map, Index a, Index b) as an (n, 2) int64 array: og_line_cells_index, pinned to the reference's compiled
+    code by tests/test_oracle_refpin.py"""
+    n = max(abs(b[0] - a[0]), abs(b[1] - a[1])) + 1
+    out = np.zeros(2 * n, np.int32)
+    m = lib().og_line_cells_index((C.c_int * 2)(*a), (C.c_int * 2)(*b), out.ctypes.data_as(C.POINTER(C.c_int)), n)
+    assert m == n
+    return out.reshape(n, 2).astype(np.int64)
+
+
 def circle_cells(g, c, r, reference=False):
     fn = ref_gridmap().refgm_circle_cells if reference else lib().og_circle_cells
     return _cells(fn, C.byref(g), d2(*c), r)

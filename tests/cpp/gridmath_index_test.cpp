@@ -2,7 +2,10 @@
 //   map_to_buffer(x, s, n) == wrap_index(x + s, n) and buffer_to_map is its inverse, for every start and every index of
 //   n in {1, 2, 63, 64, 65, 130};
 //   buffer_lin / map_cell_of the same on a 130 x 70 map, every (s0, s1) from {0, 1, 63, 64, 65, size - 1} per axis, against
-//   buffer_index / unwrap_index of a Geom with that start.
+//   buffer_index / unwrap_index of a Geom with that start;
+//   the line cursor (index_line_cursor, _offset, _step), placed at every t0 that is a multiple of 8 and stepped 8 cells, over
+//   every pair of end points of a 13 x 13 box and lines with D = 65535, A in {0, 1, 32767, 65534, 65535}: its offsets equal
+//   index_line_cell, its turn flag the difference of index_line_minor at t + 1 and at t.
 #include <cstdio>
 #include <set>
 #include <vector>
@@ -63,6 +66,36 @@ int main() {
           ++checked;
         }
     }
+  // the line cursor: every pair of end points of a 13 x 13 box, and lines with D = 65535
+  std::vector<IndexLine> lines;
+  for (int a = 0; a < 169; ++a)
+    for (int b = 0; b < 169; ++b) {
+      const int s[2] = {a % 13, a / 13}, e[2] = {b % 13, b / 13};
+      lines.push_back(index_line(s, e));
+    }
+  for (int A : {0, 1, 32767, 65534, 65535})
+    for (int k = 0; k < 4; ++k) {   // either major axis, either direction
+      const int s[2] = {7, -3}, d[2] = {(k & 1) ? A : 65535, (k & 1) ? 65535 : A};
+      const int e[2] = {(k & 2) ? s[0] - d[0] : s[0] + d[0], (k & 2) ? s[1] + d[1] : s[1] - d[1]};
+      lines.push_back(index_line(s, e));
+      CHECK(lines.back().D == 65535 && lines.back().A == A);
+    }
+  for (const IndexLine& ln : lines) {
+    if (ln.D == 0) continue;   // (a single cell: nothing to walk)
+    for (int t0 = 0; t0 <= ln.D; t0 += 8) {
+      LineCursor cur = index_line_cursor(ln, t0);
+      for (int t = t0; t < t0 + 8 && t <= ln.D; ++t) {
+        int d[2], c[2];
+        index_line_cursor_offset(ln, cur, d);
+        index_line_cell(ln, t, c);
+        CHECK(cur.t == t && ln.s[0] + d[0] == c[0] && ln.s[1] + d[1] == c[1]);
+        const bool turn = index_line_cursor_step(ln, cur);
+        if (t < ln.D) CHECK((int)turn == index_line_minor(ln, t + 1) - index_line_minor(ln, t));
+        ++checked;
+      }
+    }
+  }
+
   if (fails) {
     std::printf("gridmath index: %d checks FAILED\n", fails);
     return 1;

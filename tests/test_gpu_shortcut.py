@@ -11,7 +11,6 @@ plain Python:
 line() comes from the oracle's og_line_cells_index (pinned to the reference's compiled LineIterator), the masks from
 Engine.nbr_mask, clr from Engine.clearance_download, everything un-rotated to map space as tests/test_gpu_clearance.py does.
 Maps are 130 x 70 cells: 3 x 2 ragged tiles, the smallest shape with tile borders and ragged edges in both directions."""
-import ctypes as C
 import os
 import subprocess
 
@@ -38,15 +37,6 @@ def make(R, master=None, pos=(0.0, 0.0), rows=ROWS, cols=COLS):
     return make_engine(R, rows, cols, master, pos)
 
 
-def line(a, b):
-    """cells of LineIterator(map, Index a, Index b) as an (n, 2) array"""
-    n = max(abs(b[0] - a[0]), abs(b[1] - a[1])) + 1
-    out = np.zeros(2 * n, np.int32)
-    m = O.lib().og_line_cells_index((C.c_int * 2)(*a), (C.c_int * 2)(*b), out.ctypes.data_as(C.POINTER(C.c_int)), n)
-    assert m == n
-    return out.reshape(-1, 2).astype(np.int64)
-
-
 class Oracle:
     """the sequential definition over the engine's present masks (and clearance field), in map space"""
 
@@ -67,7 +57,7 @@ class Oracle:
     def los(self, a, b):
         key = (a, b)
         if key not in self.memo:
-            c = line(a, b)
+            c = O.line_cells_index(a, b)
             ok = True
             if len(c) > 1:
                 d = np.diff(c, axis=0)
@@ -78,7 +68,7 @@ class Oracle:
         return self.memo[key]
 
     def line_clearance(self, a, b):
-        c = line(a, b)
+        c = O.line_cells_index(a, b)
         return int(self.clr[c[:, 1], c[:, 0]].min())
 
     def path_clearance(self, p, a, m):

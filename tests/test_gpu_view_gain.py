@@ -6,7 +6,6 @@ the map or outside the disc and after an opaque one, count the union.  Integers 
 The oracle is vectorised over the rays of a view point (Want.record); a cell-by-cell walk of the same definition
 (walk_record) checks it.  The maps are small (130 x 70: 3 x 2 ragged tiles) with few view points at R = 127 and many at
 small R; one 300 x 280 map holds an R = 127 window wholly inside."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -26,15 +25,6 @@ RADII = (1, 15, 16, 31, 32, 63, 64, 127)       # the word edges of 2R + 1: 3, 31
 
 
 # ---- the lines ----
-def _line(a, b):
-    """cells of LineIterator(map, Index a, Index b), an [n, 2] array"""
-    n = max(abs(b[0] - a[0]), abs(b[1] - a[1])) + 1
-    out = np.zeros(2 * n, np.int32)
-    m = O.lib().og_line_cells_index((C.c_int * 2)(*a), (C.c_int * 2)(*b), out.ctypes.data_as(C.POINTER(C.c_int)), n)
-    assert m == n
-    return out.reshape(n, 2).astype(np.int64)
-
-
 _rings = {}
 
 
@@ -45,13 +35,13 @@ def ring_lines(radius):
         Rr = radius
         ring = [(a, b) for a in range(-Rr, Rr + 1) for b in range(-Rr, Rr + 1) if max(abs(a), abs(b)) == Rr]
         assert len(ring) == 8 * Rr and len(set(ring)) == 8 * Rr
-        lines = np.stack([_line((0, 0), off)[1:] for off in ring])
+        lines = np.stack([O.line_cells_index((0, 0), off)[1:] for off in ring])
         assert lines.shape == (8 * Rr, Rr, 2) and all(tuple(lines[k, -1]) == ring[k] for k in range(8 * Rr))
         step = max(1, (8 * Rr) // 61)
         for v in ((129, 69), (5, 64), (77, 3), (0, 0), (-40, 211)):
             for k in range(0, 8 * Rr, step):
                 off = ring[k]
-                assert np.array_equal(_line(v, (v[0] + off[0], v[1] + off[1]))[1:], lines[k] + np.array(v)), (v, off)
+                assert np.array_equal(O.line_cells_index(v, (v[0] + off[0], v[1] + off[1]))[1:], lines[k] + np.array(v)), (v, off)
         _rings[radius] = lines
     return _rings[radius]
 
@@ -112,7 +102,7 @@ class Want:
             for b in range(-radius, radius + 1):
                 if max(abs(a), abs(b)) != radius:
                     continue
-                for ci, cj in _line((vi, vj), (vi + a, vj + b))[1:]:
+                for ci, cj in O.line_cells_index((vi, vj), (vi + a, vj + b))[1:]:
                     ci, cj = int(ci), int(cj)
                     if not (0 <= ci < self.rows and 0 <= cj < self.cols) or (ci - vi) ** 2 + (cj - vj) ** 2 > radius * radius:
                         break

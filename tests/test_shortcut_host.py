@@ -45,15 +45,6 @@ def test_struct_layout_abi_version_and_profile_slots(capi, tmp_path):
     assert got[8] == len(capi.KERNELS) == 12 and capi.KERNELS[-1] == "footprint"      # no new profile slot
 
 
-def oracle_line(a, b):
-    s, e = (C.c_int * 2)(*a), (C.c_int * 2)(*b)
-    n = max(abs(b[0] - a[0]), abs(b[1] - a[1])) + 1
-    out = np.zeros(2 * n, np.int32)
-    m = O.lib().og_line_cells_index(s, e, out.ctypes.data_as(C.POINTER(C.c_int)), n)
-    assert m == n
-    return out.reshape(-1, 2)
-
-
 def test_line_cells_index_equals_the_oracle_on_every_pair_of_a_13_box(capi):
     """every ordered pair of cells of a 13 x 13 box: all octants, D / 2 odd and even, A == D, D == 0"""
     L = capi.lib()
@@ -65,7 +56,7 @@ def test_line_cells_index_equals_the_oracle_on_every_pair_of_a_13_box(capi):
         sa = (C.c_int32 * 2)(*a)
         for b in cells:
             n = L.rna_line_cells_index(sa, (C.c_int32 * 2)(*b), p, 13)
-            want = oracle_line(a, b)
+            want = O.line_cells_index(a, b)
             assert n == len(want) and np.array_equal(buf[:2 * n].reshape(-1, 2), want), (a, b)
             d = np.abs(np.diff(want, axis=0))
             assert (d.max(axis=1) == 1).all() if n > 1 else n == 1                # consecutive cells are king moves
@@ -78,13 +69,13 @@ def test_line_cells_index_equals_the_oracle_on_random_long_lines(capi):
     for _ in range(300):
         a = tuple(int(v) for v in rng.integers(0, 4096, 2))
         b = tuple(int(v) for v in rng.integers(0, 4096, 2))
-        assert np.array_equal(capi.line_cells_index(a, b), oracle_line(a, b)), (a, b)
+        assert np.array_equal(capi.line_cells_index(a, b), O.line_cells_index(a, b)), (a, b)
     for a, b in (((-7, 3), (5, -9)), ((0, 0), (70000, 69999)), ((100000, 5), (3, 70001)), ((4095, 0), (0, 4095))):
-        assert np.array_equal(capi.line_cells_index(a, b), oracle_line(a, b)), (a, b)     # negative and beyond-16-bit coordinates
+        assert np.array_equal(capi.line_cells_index(a, b), O.line_cells_index(a, b)), (a, b)     # negative and beyond-16-bit coordinates
     # only the first cap cells are written, the length is returned all the same
     buf = np.full(8, -1, np.int32)
     n = capi.lib().rna_line_cells_index((C.c_int32 * 2)(0, 0), (C.c_int32 * 2)(9, 4), buf.ctypes.data_as(C.POINTER(C.c_int32)), 3)
-    assert n == 10 and np.array_equal(buf[:6].reshape(-1, 2), oracle_line((0, 0), (9, 4))[:3]) and (buf[6:] == -1).all()
+    assert n == 10 and np.array_equal(buf[:6].reshape(-1, 2), O.line_cells_index((0, 0), (9, 4))[:3]) and (buf[6:] == -1).all()
 
 
 def test_argument_checks_that_need_no_device(capi):
