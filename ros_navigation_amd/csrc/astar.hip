@@ -336,9 +336,9 @@ int launch_chunk(rna_engine* e, const rna_astar_query* q_dev, int n, int32_t* pa
     RNA_HIP(e, hipStreamWaitEvent(search, a.ev_prep, 0));
   }
   if (s.retry_flag) *s.retry_flag = 0;
+  // search kernel, the count of searches to repeat to pinned host memory, trace kernel: the trace kernel reads the ring entry's
+  // launch order and masks, so the entry is free -- and the stage done -- only behind it
   RNA_TRY(tsa_search(e, slot, r, search, q_dev, n, paths_dev, max_len, res_dev));
-  // the count of searches to repeat travels to pinned host memory behind the search (before the stage's `done` event)
-  if (s.retry_armed) RNA_HIP(e, hipMemcpyAsync(s.retry_flag, tsa_retry_count(e, slot), sizeof(int), hipMemcpyDeviceToHost, search));
   if (pipelined) {
     RNA_HIP(e, hipEventRecord(a.ring[r].free, search));
     a.ring[r].used = true;

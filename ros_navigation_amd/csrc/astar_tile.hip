@@ -1328,8 +1328,11 @@ constexpr int TSA_FOUND = -1000;        // provisional status inside the search 
 // until the path leaves the tile -- a path of 2 000 cells is ~100 tile loads instead of 2 000 dependent
 // HBM round trips.
 constexpr int BW = TI + 2;   // LDS row pitch of the backtrace image (halo included)
-// (run by the first wavefront of the query's search workgroup once the search has ended -- the other wavefronts have
-// left, the workgroup's queue memory holds the LDS image; r = the provisional result)
+constexpr int TSA_TRACE_IMAGE_WORDS = BW * (TJ + 2) + TILE_WORDS / 4;   // one walk's LDS image: the tile with its halo ring, then the tile's 1 024 mask bytes
+static_assert((BW * (TJ + 2)) % 4 == 0 && TSA_TRACE_IMAGE_WORDS % 4 == 0, "the masks of an image, and the next image, start on 16 bytes");
+// (run by one wavefront once the query's search has ended: a wavefront of tsa_trace_kernel, whose workgroup's dynamic LDS holds
+// the image, or -- latency and retry instantiations -- the first wavefront of the search workgroup itself, the other wavefronts
+// gone and the image in the workgroup's queue memory; r = the provisional result)
 __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const TsaStage& S, const int sl, const int q, const rna_astar_result r,
                                                    const int lane, unsigned* s_tile, unsigned char* s_mask) {
   const int rows = A.rows, cols = A.cols, tiles_i = A.tiles_i, tiles_j = A.tiles_j;
@@ -1347,6 +1350,7 @@ __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const Tsa
   const int off = di + dj * BW;
   int len = 0;
   bool ok = true, done = false;
+  asm volatile("; TSA_WALK begin");   // (a comment in the assembly: tests/test_astar_trace_kernel_host.py looks for the kernels that hold the walk)
 #ifdef RNA_TSA_STATS
   unsigned long long bt_loads = 0, bt_load_ticks = 0;
 #endif
@@ -1434,8 +1438,15 @@ __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const Tsa
   if (lane == 0) A.results[q] = rna_astar_result{0, len, r.cost, r.expanded, r.rounds, r.buckets};
 }
 
+// Where a found path is traced.  The pipelined first pass (8 wavefronts, not a retry) hands it to tsa_trace_kernel: it leaves
+// "found, path pending" in the result record -- status 0 with path_len 0; a traced path has at least one cell, also where start ==
+// goal -- and all eight wavefronts return, so the walk is not in its code at all.  The latency instantiation (16 wavefronts: one
+// stream, small batches) and the retry pass, which runs after the trace kernel has gone by, keep the walk inside.
+__host__ __device__ constexpr bool tsa_trace_inside(int waves, bool retry) { return retry || waves != TSA_WAVES; }
+
 // One workgroup of 8 wavefronts per query, four of them per CU.  The workgroup first resets the tile-map entries the slot's
-// previous search made, then searches; its first wavefront traces the path at the end (tsa_backtrace_wave).
+// previous search made, then searches; the path is traced by tsa_trace_kernel behind it, or where tsa_trace_inside says so by
+// the workgroup's first wavefront at the end (tsa_backtrace_wave).
 // WAVES = wavefronts per workgroup (= per query): 8 when batches are pipelined (four queries share a CU, the throughput
 // configuration), 16 for a single batch on the engine's own stream and for batches of <= 32 queries (latency is what
 // counts there).
@@ -1734,22 +1745,54 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
     }
     return;
   }
-  // found: the first wavefront traces the path over the exact field (the queue memory holds the LDS image of the walk)
-  __syncthreads();
-  if (wv != 0) return;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  // The walk is ONE chain of dependent instructions (a step: two LDS reads, a ballot, a lane read, a handful of scalar
-  // instructions), run by one wavefront while its workgroup's LDS and query slot stay taken: at the priority of the seven
-  // search wavefronts it shares its SIMD with, a step took 0.88 us and a path of 2 000 cells 2 ms -- 18 % of the workgroup's
-  // residence (profiles/r05_search_job_stats.txt).  At the highest issue priority it gets its instructions in when it asks.
+  if constexpr (!tsa_trace_inside(WAVES, RETRY)) {
+    // found: the whole record but the path, which tsa_trace_kernel traces behind this kernel over the exact field this search
+    // leaves in the slot's pages (path_len 0 marks it pending).  Every wavefront leaves: the workgroup's wave slots and LDS are
+    // free for the next search at once.
+    if (tid == 0) {
+      results[q] = rna_astar_result{0, 0, r.cost, r.expanded, r.rounds, r.buckets};
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  } else {
+    // found: the first wavefront traces the path over the exact field (the queue memory holds the LDS image of the walk)
+    __syncthreads();
+    if (wv != 0) return;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_setprio(TSA_BT_PRIO);   // (see tsa_trace_kernel)
+#ifdef RNA_TSA_STATS
+    const unsigned long long t_bt0 = wall_clock64();
+#endif
+    tsa_backtrace_wave(A, S, sl, q, r, lane, s_node, reinterpret_cast<unsigned char*>(s_node + BW * (TJ + 2)));
+#ifdef RNA_TSA_STATS
+    if (lane == 0) { atomicAdd(&g_tsa_stat[24], wall_clock64() - t_bt0); atomicAdd(&g_tsa_stat[25], 1ull); atomicAdd(&g_tsa_stat[26], wall_clock64() - t_kernel0); }
+#endif
+  }
+}
+
+// The paths of a pipelined batch, behind its search kernel on the stage's stream: one wavefront per path, TSA_TRACE_PATHS of them
+// per workgroup.  Wavefront w of workgroup g serves the query at position P g + w of the batch's launch order (longest expected
+// search first, so one workgroup's paths are of similar length); it walks where the search left "found, path pending" and leaves
+// every other record alone (statuses 1, 2, 4 and 5 are final as the search kernel wrote them; a 5 is answered by the retry pass).
+// The walk is ONE chain of dependent instructions (a step: two LDS reads, a ballot, a lane read, a handful of scalar
+// instructions).  Inside the search kernel it was run by the workgroup's first wavefront while the workgroup's 37.6 KB of LDS and
+// its place on the CU stayed taken and the seven wave slots the other wavefronts had given back stood empty, since a new search
+// workgroup needs all eight at once: at the priority of the search wavefronts it shared its SIMD with, a step took 0.88 us and a
+// path of 2 000 cells 2 ms -- 18 % of the workgroup's residence (profiles/r05_search_job_stats.txt) --, at the highest issue
+// priority, where it gets its instructions in when it asks, 1.05 ms.  Here eight walks fill the eight wave slots of one search
+// workgroup (two wavefronts per SIMD at <= 64 VGPRs), and their eight images fit the LDS beside three resident search workgroups
+// (tests/test_astar_trace_kernel_host.py).
+constexpr int TSA_TRACE_PATHS = 8;
+__global__ void __launch_bounds__(TSA_TRACE_PATHS * 64) __attribute__((amdgpu_waves_per_eu(TSA_WAVES_PER_EU, TSA_WAVES_PER_EU))) tsa_trace_kernel(const TsaLaunch A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned s_image[];   // TSA_TRACE_PATHS images of TSA_TRACE_IMAGE_WORDS, sized by the launch
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int rank = (int)blockIdx.x * TSA_TRACE_PATHS + wv;
+  if (rank >= A.n) return;
+  const int q = __builtin_amdgcn_readfirstlane(A.S.perm[rank]);
+  const rna_astar_result r = A.results[q];
+  if (r.status != 0 || r.path_len != 0) return;
   __builtin_amdgcn_s_setprio(TSA_BT_PRIO);
-#ifdef RNA_TSA_STATS
-  const unsigned long long t_bt0 = wall_clock64();
-#endif
-  tsa_backtrace_wave(A, S, sl, q, r, lane, s_node, reinterpret_cast<unsigned char*>(s_node + BW * (TJ + 2)));
-#ifdef RNA_TSA_STATS
-  if (lane == 0) { atomicAdd(&g_tsa_stat[24], wall_clock64() - t_bt0); atomicAdd(&g_tsa_stat[25], 1ull); atomicAdd(&g_tsa_stat[26], wall_clock64() - t_kernel0); }
-#endif
+  unsigned* const s_tile = s_image + wv * TSA_TRACE_IMAGE_WORDS;
+  tsa_backtrace_wave(A, A.S, q, q, r, lane, s_tile, reinterpret_cast<unsigned char*>(s_tile + BW * (TJ + 2)));
 }
 
 // |{n : g(n) + h(n) <= f*}| per query from the pages still resident in HBM (measurement utility)
@@ -1946,7 +1989,8 @@ int tsa_order(rna_engine* e, int d, int ring, hipStream_t st, const rna_astar_qu
   RNA_HIP(e, hipGetLastError());
   return RNA_OK;
 }
-// The search itself; the stage remembers the launch for its second passes (tsa_retry_launch) and for tsa_settled.
+// The search itself, the copy of its retry count to the host and -- pipelined -- the trace kernel behind them, all on `st`; the
+// stage remembers the launch for its second passes (tsa_retry_launch) and for tsa_settled.
 int tsa_search(rna_engine* e, int d, int ring, hipStream_t st, const rna_astar_query* q_dev, int n, int32_t* paths_dev, int max_len,
                rna_astar_result* res_dev) {
   AstarDevice& a = e->astar;
@@ -1975,9 +2019,18 @@ int tsa_search(rna_engine* e, int d, int ring, hipStream_t st, const rna_astar_q
   // takes 9.1 instead of 12.9 ms), 8 where throughput does (16 in the pipeline: 91.6 k instead of 122.8 k cycles/s)
   static const bool wide_env = getenv("RNA_TSA_WIDE") != nullptr;   // developer knob: 16 wavefronts per query always
   const bool wide = wide_env || n <= 32;
-  if (a.depth > 1 && !wide) hipLaunchKernelGGL((tsa_search_kernel<TSA_WAVES, false>), dim3(n), dim3(TSA_WAVES * 64), lds_dyn, st, A);
+  const bool throughput = a.depth > 1 && !wide;
+  if (throughput) hipLaunchKernelGGL((tsa_search_kernel<TSA_WAVES, false>), dim3(n), dim3(TSA_WAVES * 64), lds_dyn, st, A);
   else hipLaunchKernelGGL((tsa_search_kernel<16, false>), dim3(n), dim3(16 * 64), lds_dyn, st, A);
   RNA_HIP(e, hipGetLastError());
+  // the count of searches to repeat travels to pinned host memory behind the search (before the stage's `done` event)
+  if (can_retry) RNA_HIP(e, hipMemcpyAsync(s.retry_flag, A.retry_count, sizeof(int), hipMemcpyDeviceToHost, st));
+  // the paths of the searches that handed theirs over (inside this function's timer: a launch's time has always included its walks)
+  if (throughput && !tsa_trace_inside(TSA_WAVES, false)) {
+    hipLaunchKernelGGL(tsa_trace_kernel, dim3((n + TSA_TRACE_PATHS - 1) / TSA_TRACE_PATHS), dim3(TSA_TRACE_PATHS * 64),
+                       (size_t)TSA_TRACE_PATHS * TSA_TRACE_IMAGE_WORDS * sizeof(unsigned), st, A);
+    RNA_HIP(e, hipGetLastError());
+  }
   memcpy(s.last_launch, &A, sizeof(A));
   s.last_lds = lds_dyn;
   s.last_retried = 0;
