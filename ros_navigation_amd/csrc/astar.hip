@@ -361,9 +361,6 @@ int launch_chunk(rna_engine* e, const rna_astar_query* q_dev, int n, int32_t* pa
 }  // namespace
 
 namespace rna {
-#ifdef RNA_TSA_STATS
-void tsa_stats_dump();
-#endif
 // every stream is idle (sync_all): second passes that are due go out and are waited for
 int astar_settle(rna_engine* e) {
   AstarDevice& a = e->astar;
@@ -376,9 +373,6 @@ int astar_release(rna_engine* e) {
   (void)sync_all(e);
   stage_trace_dump();
   g_trace.dump();
-#ifdef RNA_TSA_STATS
-  tsa_stats_dump();
-#endif
   for (AstarStage& s : a.stage) free_stage(s);
   if (a.ev_init) { (void)hipEventDestroy(a.ev_init); a.ev_init = nullptr; }
   if (a.ev_prep) { (void)hipEventDestroy(a.ev_prep); a.ev_prep = nullptr; }

@@ -271,22 +271,6 @@ __global__ void __launch_bounds__(256) tsa_zero_page0_kernel(unsigned* __restric
   if (threadIdx.x < AUX_WORDS / 4) reinterpret_cast<uint4*>(paux + page0 * AUX_WORDS)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-#ifdef RNA_TSA_STATS
-// developer build: phase timers (100 MHz wall clock ticks summed over all jobs), printed by the host
-__device__ unsigned long long g_tsa_stat[32];
-#define TSA_T(var) const unsigned long long var = wall_clock64()
-#define TSA_ACC(slot, t0, t1) tsa_acc[slot] += (unsigned long long)((t1) - (t0))
-#define TSA_CNT(slot, v) tsa_acc[slot] += (unsigned long long)(v)
-#define TSA_ACC_PARAM , unsigned long long* tsa_acc
-#define TSA_ACC_ARG , tsa_acc
-#else
-#define TSA_ACC_PARAM
-#define TSA_ACC_ARG
-#define TSA_T(var)
-#define TSA_ACC(slot, t0, t1)
-#define TSA_CNT(slot, v)
-#endif
-
 // ---- scheduler of the one-workgroup-per-query kernel: an open list of tiles in LDS ----
 // Per query (= workgroup), in LDS:
 //   st2    two bits per tile: D "a wake-up is pending" (bit 0), R "a wavefront is running the tile" (bit 1)
@@ -638,7 +622,7 @@ __device__ __forceinline__ unsigned long long tsa_row_fixpoint(int& g, int& pp, 
 #define TSA_PP(b) TSA_CAT(pp, b)
 #define TSA_MKW(b) TSA_CAT(TSA_MK_, b)   // the mask word that holds row b's byte, at bit 8 * (b & 3)
 __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const int lane_in, const int t_in, const TsaCtx& C,
-                                       const int first_in, const unsigned bucket_end, const int key_base, const int key_shift, int* spare TSA_ACC_PARAM) {
+                                       const int first_in, const unsigned bucket_end, const int key_base, const int key_shift, int* spare) {
   // STICKY TILES (round 5).  A tile that is woken while its job runs used to be queued again by its wavefront (class 0)
   // and, as a rule, taken again at once by the same wavefront: a push, a pop, a claim, the sixteen rows, the masks and the
   // sixteen pass-on values loaded and formed again -- for a third of all jobs (scripts/sim_async.c: 36 % of the jobs are
@@ -673,7 +657,6 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
   // recomputed here instead of being hoisted out of the job loop, kept alive across the sweeps and spilled to scratch
   int lane = lane_in;
   asm volatile("" : "+v"(lane));
-  TSA_T(t_a);
   asm volatile("; TSA_MARK job_begin");
   // ---- 1. page table look-up of the eight neighbouring tiles (lane k < 8: direction k; 0 = none or outside) and of
   //         the tile itself (lane 8) ----
@@ -764,8 +747,6 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
 #define TSA_HT(b) TSA_HC(b, thr)   /* a cell passes on iff u >= h + thr */
   // bit b: this lane's cell in row b is free (and inside the map) -- from the snapshot, loaded with the masks
   const unsigned fbits = fbits_ld;
-  TSA_T(t_h0);
-  TSA_ACC(9, t_a, t_h0);   // issuing the loads + waiting for them
   asm volatile("; TSA_MARK halo_begin");
   // ---- 4. what the halo can contribute (once: it does not change during the job) ----
   // rows to evaluate in the next down / up sweep: a row is evaluated from above when the row above it changed (or it
@@ -849,7 +830,6 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
     const unsigned long long upT = __builtin_amdgcn_ballot_w64(cT > g0), upB = __builtin_amdgcn_ballot_w64(cB > g15);
     const unsigned long long imask = __builtin_amdgcn_ballot_w64(cX > gcol);
     if (!(upT | upB | imask) && !planted && !first) {   // the wake-up brought nothing better
-      TSA_CNT(10, 1); if (sticky) TSA_CNT(23, 1); TSA_T(t_n); TSA_ACC(15, t_a, t_n);
       goto tsa_job_done;   // (counted in TsaLocalSched::finish like every turn; the jobs that get past this point are counted at the end of the job)
     }
     asm volatile("; TSA_MARK noop_decided");
@@ -947,17 +927,7 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
     nd |= (rel | (rel << 1)) & 0xffffu;
     nu |= rel >> 1;
   }
-  TSA_T(t_b);
-  TSA_ACC(0, t_a, t_b);
   // ---- 5. sweeps ----
-#ifdef RNA_TSA_STATS
-  int evals = 0, hpass = 0;
-#define TSA_STAT_INC(v) v += 1
-#define TSA_STAT_HP(left) hpass += (left) ? TSA_HPASS - 1 - (31 - __builtin_clz(left)) : TSA_HPASS   /* passes that moved something */
-#else
-#define TSA_STAT_INC(v)
-#define TSA_STAT_HP(left)
-#endif
   // the (negative) step costs live in VGPRs: v_add_u32 with a DPP source cannot take a literal, and only then does the
   // wave shift fold into the add (one instruction instead of v_mov_dpp + v_add)
   int nS = -COST_S, nD = -COST_D;
@@ -979,7 +949,6 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
         (lane_p1(TSA_PP(src)) + nD) & TSA_OPEN(TSA_MKW(b), 8 * ((b) & 3) + (kC)))
 #define TSA_ROW(b, VERT, AGVAR, DIR)                                                                                \
   {                                                                                                              \
-    TSA_STAT_INC(evals);                                                                                         \
     const int open_ = TSA_OPEN(fbits, b);                                                                        \
     const int mv_ = VERT;                                                                                        \
     const int m_ = max3i(mv_, lane_m1(TSA_PP(b)) + nS, lane_p1(TSA_PP(b)) + nS) & open_;                         \
@@ -1019,10 +988,8 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
             : [nS] "v"(nS), [open] "v"(open_), [ht] "v"(ht_)                                                     \
             : "vcc", "scc");                                                                                     \
       }                                                                                                          \
-      TSA_STAT_HP(left_);                                                                                        \
       if (TSA_UNLIKELY(left_ == 0u)) {   /* the one-cell passes ran out while the row was still moving: the rest in one scan */ \
         if (scan_ok) {                                                                                           \
-          TSA_CNT(14, 1);                                                                                        \
           up_ |= tsa_row_fixpoint(TSA_G(b), TSA_PP(b), open_, ht_, thr, lane);                                   \
         } else {                                                                                                 \
           AGVAR |= 1u << (b);                                                                                    \
@@ -1061,14 +1028,6 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
 #undef TSA_UP
 #undef TSA_ROW
 #undef TSA_VERT
-#undef TSA_STAT_INC
-#undef TSA_STAT_HP
-  TSA_T(t_c);
-  TSA_ACC(1, t_b, t_c);
-  TSA_CNT(8, evals);
-  TSA_CNT(11, hpass);
-  if (first) { TSA_CNT(18, 1); TSA_CNT(19, evals); TSA_CNT(20, __builtin_popcount(rowchg)); }   // first jobs: how many, their evaluations, the rows they changed
-  TSA_CNT(21, __builtin_popcount(rowchg));
   asm volatile("; TSA_MARK results_begin");
   // ---- 6. results: rows that changed, the edge-column copies, the goal ----
   asm volatile("" : "+v"(lane));
@@ -1142,7 +1101,6 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
 #undef TSA_GOAL
     }
   }
-  TSA_T(t_w0);
   asm volatile("; TSA_MARK wake_begin");
   // ---- 7. who has to run: neighbours whose halo got better (or may pass on now), this tile again in a later bucket ----
   {
@@ -1267,17 +1225,10 @@ __device__ __forceinline__ void tsa_job(TsaLocalSched& sch, unsigned* scr, const
       kf = __builtin_amdgcn_inverse_ballot_w64(0x40ull) ? kfS : kf;
       int key = (key_base - kf) >> key_shift;
       key = key < 0 ? 0 : (key > TSA_NCLS - 1 ? TSA_NCLS - 1 : key);
-      TSA_T(t_w1);
       sch.wake8(__builtin_amdgcn_inverse_ballot_w64((unsigned long long)wm), nb_t, (unsigned)key, lane, spare);
-      TSA_T(t_w2);
-      TSA_ACC(3, t_w1, t_w2);   // queueing the wake-ups
-      TSA_CNT(13, 1);
     }
   }
   asm volatile("; TSA_MARK job_end");
-  TSA_T(t_d);
-  TSA_ACC(2, t_c, t_d);
-  TSA_ACC(6, t_w0, t_d);   // wake tests + queueing
   if (lane_in == 0) { atomicAdd(&scr[SCR_CNT], (unsigned)__builtin_popcount(rowchg)); atomicAdd(&scr[SCR_CNT + 1], 1u); }   // rows written, jobs that got past the halo step (this wavefront's own words; adds that return nothing)
   }
 tsa_job_done:
@@ -1290,8 +1241,6 @@ tsa_job_done:
     if (!again) break;
     first_w = again >> 1;
     sticky_w = 1;
-    TSA_CNT(7, 1);    // (a sticky turn counts as a job of its own in the developer build's figures)
-    TSA_CNT(22, 1);
   }
   }   // next turn on the same tile
 #undef TSA_ROW_CHANGED
@@ -1351,13 +1300,7 @@ __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const Tsa
   int len = 0;
   bool ok = true, done = false;
   asm volatile("; TSA_WALK begin");   // (a comment in the assembly: tests/test_astar_trace_kernel_host.py looks for the kernels that hold the walk)
-#ifdef RNA_TSA_STATS
-  unsigned long long bt_loads = 0, bt_load_ticks = 0;
-#endif
   while (ok && !done) {
-#ifdef RNA_TSA_STATS
-    const unsigned long long t_l0 = wall_clock64();
-#endif
     // ---- tile of the current cell + halo ring + masks -> LDS ----
     const int ti = ci >> 6, tj = cj >> 4;
     const int t = tj * tiles_i + ti;
@@ -1395,9 +1338,6 @@ __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const Tsa
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-#ifdef RNA_TSA_STATS
-    bt_loads += 1; bt_load_ticks += wall_clock64() - t_l0;
-#endif
     // ---- walk inside the tile ----
     int il = ci & (TI - 1), jl = cj & (TJ - 1);
     unsigned uc = s_tile[(jl + 1) * BW + il + 1];
@@ -1412,7 +1352,7 @@ __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const Tsa
       const unsigned long long m = __ballot(hit);
       if (!m) { ok = false; break; }
       // (only lanes 0..7 can hit: a 32-bit bit search.  As __ffsll the index was carried as a 64-bit scalar pair whose upper half the
-      // compiler took from a register it reused inside the loop -- the -DRNA_TSA_STATS build walked in circles until `len > ncell`)
+      // compiler took from a register it reused inside the loop -- a developer build that is gone walked in circles until `len > ncell`)
       const int src = __builtin_ctz((unsigned)m);
       uc = (unsigned)__builtin_amdgcn_readlane((int)un, src);   // (src is wave-uniform: a v_readlane, not a trip through the LDS crossbar)
       const int sdi = kdi_of(src), sdj = kdj_of(src);
@@ -1420,9 +1360,6 @@ __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const Tsa
       if (il < 0 || jl < 0 || il >= TI || jl >= TJ) break;   // left the tile: load that one
     }
   }
-#ifdef RNA_TSA_STATS
-  if (lane == 0) { atomicAdd(&g_tsa_stat[27], bt_loads); atomicAdd(&g_tsa_stat[28], bt_load_ticks); atomicAdd(&g_tsa_stat[29], (unsigned long long)len); }
-#endif
   if (!ok) {
     if (lane == 0) A.results[q] = rna_astar_result{1, 0, INF, r.expanded, r.rounds, r.buckets};
     return;
@@ -1484,9 +1421,6 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
   // to be the longest (the first tickets) get the issue slots of their SIMDs first, the short ones fill in around them.
   if (__builtin_amdgcn_readfirstlane(s_rank) < A.prio_first) __builtin_amdgcn_s_setprio(3);
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef RNA_TSA_STATS
-  const unsigned long long t_kernel0 = wall_clock64();
-#endif
   const int rows = A.rows, cols = A.cols, tiles_i = A.tiles_i, tiles_j = A.tiles_j;
   rna_astar_query qu = A.queries[q];   // buffer linear indices; the search itself runs in map space
   const int ncell = rows * cols;
@@ -1564,11 +1498,6 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
   if (tid == 0) s_open[C.ts >> 5] = 1u << (C.ts & 31);   // the start tile's first job plants g(start) = 0
   __syncthreads();
 
-#ifdef RNA_TSA_STATS
-  unsigned long long tsa_acc[24] = {};
-  const unsigned long long t_life0 = wall_clock64();
-  const unsigned long long c_life0 = __builtin_amdgcn_s_memtime();
-#endif
   TsaLocalSched sch{&s_best, &s_state, s_st2, s_far, s_node, s_head, s_bm, s_qc, &s_count, &s_spill, s_open, &s_open_left};
   int spare = -1;   // a queue node this wavefront owns (the one its last job's entry sat in): its next wake-up uses it
 
@@ -1581,7 +1510,6 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
     bool idle = false;   // this wavefront is counted in s_idle
     bool open_blocked = false;
     for (;;) {
-      TSA_T(t_p0);
       if (lds_ldi(&s_state) >= 4) break;
       if (idle) {
         if (lds_ldi(&s_idle) == WAVES) break;          // every wavefront idle: nothing queued, nothing running
@@ -1661,10 +1589,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
         t = tt;
         first = r >> 1;
       }
-      TSA_T(t_p1);
-      TSA_ACC(4, t_p0, t_p1);   // taking a job
-      TSA_CNT(7, 1);
-      tsa_job(sch, s_scr[wv], lane, t, C, first, bucket_end_u, key_base, key_shift, &spare TSA_ACC_ARG);
+      tsa_job(sch, s_scr[wv], lane, t, C, first, bucket_end_u, key_base, key_shift, &spare);
       // (the tile has been released by the job itself -- or kept for further turns while wake-ups kept coming: TsaLocalSched::finish)
       // (both flags are false whenever a job is taken; said here, they are not two lane masks kept -- spilled -- across the job)
       idle = false;
@@ -1725,13 +1650,6 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
     atomicAdd(&cnt[6], (unsigned long long)(s_bucket - s_bucket0 + 1));
     if (s_reruns) atomicAdd(&cnt[7], (unsigned long long)s_reruns);
   }
-#ifdef RNA_TSA_STATS
-  tsa_acc[5] = wall_clock64() - t_life0;   // wave lifetime inside the search loop
-  tsa_acc[12] = __builtin_amdgcn_s_memtime() - c_life0;   // the same in shader clock ticks
-  if (lane == 0) for (int k = 0; k < 16; ++k) atomicAdd(&g_tsa_stat[k], tsa_acc[k]);
-  if (lane == 0) for (int k = 18; k < 24; ++k) atomicAdd(&g_tsa_stat[k], tsa_acc[k]);   // (16 / 17: per search, below)
-  if (tid == 0) { atomicAdd(&g_tsa_stat[16], (unsigned long long)s_nalloc); atomicAdd(&g_tsa_stat[17], 1ull); }   // tiles this search touched; searches
-#endif
   // what the next search in this slot has to reset
   if (tid == 0) S.nalloc[sl] = s_nalloc < C.cap ? s_nalloc : C.cap;
   // (`rounds` reports tile jobs per wavefront -- every job, also the ones that found nothing in their halo: there are no rounds any more)
@@ -1759,13 +1677,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
     if (wv != 0) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_setprio(TSA_BT_PRIO);   // (see tsa_trace_kernel)
-#ifdef RNA_TSA_STATS
-    const unsigned long long t_bt0 = wall_clock64();
-#endif
     tsa_backtrace_wave(A, S, sl, q, r, lane, s_node, reinterpret_cast<unsigned char*>(s_node + BW * (TJ + 2)));
-#ifdef RNA_TSA_STATS
-    if (lane == 0) { atomicAdd(&g_tsa_stat[24], wall_clock64() - t_bt0); atomicAdd(&g_tsa_stat[25], 1ull); atomicAdd(&g_tsa_stat[26], wall_clock64() - t_kernel0); }
-#endif
   }
 }
 
@@ -2056,34 +1968,6 @@ int tsa_counters_read(rna_engine* e, unsigned long long* out, bool reset) {
   }
   return RNA_OK;
 }
-
-#ifdef RNA_TSA_STATS
-void tsa_stats_dump() {
-  unsigned long long st[32];
-  if (hipMemcpyFromSymbol(st, HIP_SYMBOL(g_tsa_stat), sizeof(st)) != hipSuccess) return;
-  const double jobs = (double)st[7];
-  if (jobs <= 0) return;
-  const double busy = (double)(st[0] + st[1] + st[2]);
-  fprintf(stderr, "[tsa stats] per job us: loads issued + arrived %.2f (of load+halo), wake tests + queueing %.2f of which queueing %.2f (of results); jobs that queue wake-ups %.1f%%; a job that finds nothing %.2f us\n",
-          st[9] * 0.01 / jobs, st[6] * 0.01 / jobs, st[3] * 0.01 / jobs, 100.0 * (double)st[13] / jobs, st[15] * 0.01 / (double)std::max<unsigned long long>(1, st[10]));
-  fprintf(stderr, "[tsa stats] searches %.0f, tiles touched %.0f (%.1f per search), jobs per touched tile %.2f, jobs that find nothing %.3f of all\n", (double)st[17],
-          (double)st[16], (double)st[16] / (double)std::max<unsigned long long>(1, st[17]), jobs / (double)std::max<unsigned long long>(1, st[16]), (double)st[10] / jobs);
-  fprintf(stderr, "[tsa stats, tile kernel, all launches] jobs %.0f (%.1f%% no-op) | per job us: load+halo %.2f sweeps %.2f results %.2f | wave lifetime %.1f wave-ms, in jobs %.1f wave-ms (%.1f%%), taking jobs %.1f wave-ms (%.1f%%) | row evaluations per job %.1f, extra horizontal passes %.1f | shader clock while searching %.0f MHz\n",
-          jobs, 100.0 * (double)st[10] / jobs, st[0] * 0.01 / jobs, st[1] * 0.01 / jobs, st[2] * 0.01 / jobs, st[5] * 1e-5, busy * 1e-5,
-          100.0 * busy / (double)st[5], st[4] * 1e-5, 100.0 * (double)st[4] / (double)st[5], st[8] / jobs, st[11] / jobs,
-          100.0 * (double)st[12] / (double)std::max<unsigned long long>(1, st[5]));
-  if (st[25]) fprintf(stderr, "[tsa stats] backtrace (one wavefront, the workgroup's LDS held meanwhile): %.1f us per found path, %.1f %% of the workgroup's residence (%.2f ms from its first instruction to the end of the backtrace, found paths only)\n",
-                      st[24] * 0.01 / (double)st[25], 100.0 * (double)st[24] / (double)std::max<unsigned long long>(1, st[26]), st[26] * 1e-5 / (double)st[25]);
-  if (st[25]) fprintf(stderr, "[tsa stats] backtrace: %.0f cells and %.1f tile loads per path (%.1f cells per load), a tile load %.2f us (%.0f %% of the backtrace), a step %.3f us\n",
-                      (double)st[29] / (double)st[25], (double)st[27] / (double)st[25], (double)st[29] / (double)std::max<unsigned long long>(1, st[27]),
-                      st[28] * 0.01 / (double)std::max<unsigned long long>(1, st[27]), 100.0 * (double)st[28] / (double)std::max<unsigned long long>(1, st[24]),
-                      (double)(st[24] - st[28]) * 0.01 / (double)std::max<unsigned long long>(1, st[29]));
-  fprintf(stderr, "[tsa stats] sticky turns (the wavefront kept a tile that was woken while it ran) %.3f of all jobs, of which %.3f find nothing\n",
-          (double)st[22] / jobs, (double)st[23] / (double)std::max<unsigned long long>(1, st[22]));
-  fprintf(stderr, "[tsa stats] first jobs (a tile's first in a bucket: the rows a new bound releases, and what they flag) %.3f of all, %.1f row evaluations and %.1f changed rows each; rows changed per job %.1f; rows sent to the scan per job %.2f\n",
-          (double)st[18] / jobs, (double)st[19] / (double)std::max<unsigned long long>(1, st[18]), (double)st[20] / (double)std::max<unsigned long long>(1, st[18]), (double)st[21] / jobs, (double)st[14] / jobs);
-}
-#endif
 
 int tsa_settled(rna_engine* e, int slot, const rna_astar_query* q, const rna_astar_result* r, int n, int32_t* d_counts) {
   const TsaGrid G = tsa_grid(e);

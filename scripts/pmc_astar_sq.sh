@@ -10,7 +10,10 @@ mkdir -p $OUT
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_THREAD_CYCLES_VALU SQ_INSTS_SMEM"; do
   i=$((i+1))
-  timeout 200 rocprofv3 --kernel-trace --pmc $set -d $OUT/p$i -o r --output-format csv -- python3 $ROOT/scripts/astar_stats.py 4096 256 $BW > $OUT/log$i.txt 2>&1
+  timeout -k 10 200 rocprofv3 --kernel-trace --pmc $set -d $OUT/p$i -o r --output-format csv -- python3 $ROOT/scripts/astar_stats.py 4096 256 $BW > $OUT/log$i.txt 2>&1
+  rc=$?
+  # a pass that failed ends the probe: nothing more is started on the GPU and no summary is made of the passes before it
+  if [ $rc -ne 0 ]; then echo "pass $i ($set) exited $rc: stopped, no summary (see $OUT/log$i.txt)"; tail -5 $OUT/log$i.txt; exit $rc; fi
 done
 python3 - <<PY > $OUT/summary.txt
 import csv, glob, collections

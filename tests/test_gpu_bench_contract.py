@@ -214,7 +214,15 @@ def test_default_bench_keeps_the_engine_stream_alive():
     """The full-size loop, shortened: the search streams' CU mask has to leave the short engine-stream kernels (map
     update, VFH+, field reset) somewhere to run -- when four search workgroups per CU took every register of every CU,
     himm_prep took 3-6 ms instead of 0.3 ms per step and the step rate hung on the engine stream (22 k cycles/s).  Loose
-    bounds: a guard against that cliff and against the hardware-queue cliff of too many pipeline stages, not a benchmark."""
+    bounds: a guard against that cliff and against the hardware-queue cliff of too many pipeline stages, not a benchmark.
+
+    Known weakness, not yet mended: hardware queues are counted per GPU, not per process.  The bench holds 23 at 20 stages and the
+    rate falls by a fifth from 25 on (the depth sweep), so the queues of the pytest process itself, once the
+    astar test files before this one have run in it, can push the bench over: alone 176 k cycles/s, astar_search 16.0-17.0 ms, chain
+    1.09-1.13 ms; started by a process that had just run those three files 135-136 k, 21.9-24.3 ms, chain 1.13-1.70 ms; started by
+    a process that holds nothing but one used torch stream 140 k, 20.5 ms, 1.10 ms, and with four more used streams 118 k, 22.6 ms,
+    1.72 ms (himm_raster 1.09 instead of 0.50) -- the same library, the same box, seconds apart.  So the second assertion fails
+    or passes with the number of queues the runtime of the pytest process happens to have made."""
     d = default_bench()
     k = d["kernel_ms_per_pass"]
     assert k["himm_prep"] < 1.0 and k["vfh_step"] < 0.6 and k["compose_master"] < 0.6, k
