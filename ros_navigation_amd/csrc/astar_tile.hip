@@ -33,6 +33,7 @@
 // How the kernel got here (the LDS worklist kernel of round 1, the dense sweeps and red-black rounds of round 2):
 // docs/history.md; the measurements of round 3: DESIGN.md 5.
 #include "engine.hpp"
+#include "astar_trace_parent.hpp"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -56,6 +57,7 @@ constexpr int TSA_BT_PRIO = 3;        // issue priority of the wavefront that tr
 constexpr int TSA_SCOPE = __HIP_MEMORY_SCOPE_AGENT;   // scope the loads of the search field are coherent at: every load goes to L2 (sc1), see ld_l2
 constexpr int TSA_MAX_TILE_WORDS = 2048;   // active-tile bitset words -> up to 65536 tiles
 constexpr int COST_S = 1000, COST_D = 1414;
+static_assert(COST_S == (int)TSA_PARENT_COST_S && COST_D == (int)TSA_PARENT_COST_D && TI == 64 && TJ == 16, "astar_trace_parent.hpp and the walk's il + 256 jl are written for these");
 constexpr int INF = 0x7fffffff;
 constexpr int KU = 0x40000000;             // field word u = KU - g; 0 = unreached
 constexpr int SCR_CNT = 84 + 192 + 48 + 64;     // four counters behind the scratch proper: rows written, jobs that got past the halo step, all turns
@@ -155,6 +157,9 @@ __device__ __forceinline__ int tsa_prop(int u, int h, int thr) { return (u - h >
 
 __device__ __forceinline__ int tile_of(int i, int j, int tiles_i) { return (j >> 4) * tiles_i + (i >> 6); }
 __device__ __forceinline__ int in_page(int i, int j) { return ((j & 15) << 6) + (i & 63); }
+// v_writelane: lane `sel` (wave-uniform) of `old` becomes the wave-uniform `v`.  The compiler has the intrinsic and no builtin of
+// that name for it, so it is declared by its name in the intermediate code; the compiler then places it and pads it like any other.
+extern "C" __device__ int tsa_writelane(int v, int sel, int old) __asm("llvm.amdgcn.writelane.i32");
 // neighbouring tile k (same numbering as the neighbour-mask bits): offsets along i and j
 __device__ __forceinline__ int kdi_of(int k) { return (k == 0 || k == 3 || k == 5) ? -1 : ((k == 2 || k == 4 || k == 7) ? 1 : 0); }
 __device__ __forceinline__ int kdj_of(int k) { return k < 3 ? -1 : (k > 4 ? 1 : 0); }
@@ -1272,10 +1277,19 @@ struct TsaLaunch {
 constexpr int TSA_FOUND = -1000;        // provisional status inside the search kernel: found, path not traced yet
 
 // Canonical backtrace, one wavefront per query: walk from the goal to the neighbour n with g[n] + w(n, c) == g[c],
-// lowest linear index first (lane k probes neighbour k).  The walk runs in LDS: the 64 x 16 tile of the current
-// cell plus its halo ring and the tile's neighbour masks are loaded once, then every step is one LDS round trip
-// until the path leaves the tile -- a path of 2 000 cells is ~100 tile loads instead of 2 000 dependent
-// HBM round trips.
+// lowest linear index first.  The walk runs in LDS: the 64 x 16 tile of the current cell plus its halo ring and the
+// tile's neighbour masks are loaded once -- a path of 2 000 cells is ~70 tile loads instead of 2 000 dependent HBM
+// round trips.  Which neighbour a cell steps to depends on that image alone, so the wavefront decides it for all
+// 1 024 cells of the tile at once, before the first step (the PARENT MAP: lane = column, the sixteen rows one after
+// the other over a window of three image rows, every lane busy and no chain from one cell to the next), and writes
+// the code of each cell (tsa_parent_code, astar_trace_parent.hpp) over the cell's mask byte.  That is about as much
+// as eight steps of a walk that probes its eight neighbours at every cell, where a path stays in a tile for 29 steps
+// on average.  A step is then one byte read at a wave-uniform address, three lane reads of the per-move increments
+// (lanes 0..7 hold them) and a few scalar instructions: the cell is carried as its linear index (the start test is
+// one compare), the place in the tile as il + 256 jl, which shows a step over any of the four edges in two bits.
+// The cells of the path are parked in the lanes of one register (step n in lane n & 63) and leave 64 at a time as
+// one coalesced store.
+constexpr unsigned TSA_CODE_START = TSA_PARENT_NONE + 1u;   // code of the start's cell in a walk's parent map
 constexpr int BW = TI + 2;   // LDS row pitch of the backtrace image (halo included)
 constexpr int TSA_TRACE_IMAGE_WORDS = BW * (TJ + 2) + TILE_WORDS / 4;   // one walk's LDS image: the tile with its halo ring, then the tile's 1 024 mask bytes
 static_assert((BW * (TJ + 2)) % 4 == 0 && TSA_TRACE_IMAGE_WORDS % 4 == 0, "the masks of an image, and the next image, start on 16 bytes");
@@ -1290,17 +1304,20 @@ __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const Tsa
   const size_t page_base = (size_t)sl * ((size_t)S.cap + 1);
   const int start = tsa_unwrap_lin(A.queries[q].start, rows, cols, A.s0, A.s1);
   const int goal = tsa_unwrap_lin(A.queries[q].goal, rows, cols, A.s0, A.s1);
-  const int si = start % rows, sj = start / rows;
   int ci = goal % rows, cj = goal / rows;
+  int lin = goal;   // the current cell, map space: cj * rows + ci
   int* rev = A.rev_all + (size_t)q * A.rev_cap;
   const int k = lane & 7;
-  const int wk = (k == 1 || k == 3 || k == 4 || k == 6) ? COST_S : COST_D;
   const int di = kdi_of(k), dj = kdj_of(k);
-  const int off = di + dj * BW;
-  int len = 0;
-  bool ok = true, done = false;
+  // lane k < 8: what a step over move k adds to the linear index, to the place in the tile (il + 256 jl) and to the byte
+  // address of the cell's code in s_mask
+  const int step_lin = di + dj * rows, step_pos = di + dj * 256, step_adr = di * TJ + dj;
+  int cells = 0;   // lane l: the path's cell number (len & ~63) + l, until the 64 are stored
+  int len = 0, sel = 0;   // cells so far, and len & 63: the lane that takes the next one
+  const int si = start % rows, sj = start / rows;
+  const int start_ti = si >> 6, start_tj = sj >> 4;
   asm volatile("; TSA_WALK begin");   // (a comment in the assembly: tests/test_astar_trace_kernel_host.py looks for the kernels that hold the walk)
-  while (ok && !done) {
+  for (;;) {
     // ---- tile of the current cell + halo ring + masks -> LDS ----
     const int ti = ci >> 6, tj = cj >> 4;
     const int t = tj * tiles_i + ti;
@@ -1338,36 +1355,75 @@ __device__ __forceinline__ void tsa_backtrace_wave(const TsaLaunch& A, const Tsa
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    // ---- walk inside the tile ----
-    int il = ci & (TI - 1), jl = cj & (TJ - 1);
-    unsigned uc = s_tile[(jl + 1) * BW + il + 1];
-    for (;;) {
-      if (lane == 0 && len < A.rev_cap) rev[len] = cj * rows + ci;
-      ++len;
-      if (ci == si && cj == sj) { done = true; break; }
-      if (len > ncell || uc == 0u) { ok = false; break; }
-      const unsigned mc = s_mask[il * 16 + jl];
-      const unsigned un = s_tile[(jl + 1) * BW + il + 1 + off];
-      const bool hit = (lane < 8) & (((mc >> k) & 1u) != 0u) & (un != 0u) & (un == uc + (unsigned)wk);   // g(n) + w == g(c)  (no short circuits: one chain of compares, no exec-masked blocks in the walk)
-      const unsigned long long m = __ballot(hit);
-      if (!m) { ok = false; break; }
-      // (only lanes 0..7 can hit: a 32-bit bit search.  As __ffsll the index was carried as a 64-bit scalar pair whose upper half the
-      // compiler took from a register it reused inside the loop -- a developer build that is gone walked in circles until `len > ncell`)
-      const int src = __builtin_ctz((unsigned)m);
-      uc = (unsigned)__builtin_amdgcn_readlane((int)un, src);   // (src is wave-uniform: a v_readlane, not a trip through the LDS crossbar)
-      const int sdi = kdi_of(src), sdj = kdj_of(src);
-      ci += sdi; cj += sdj; il += sdi; jl += sdj;
-      if (il < 0 || jl < 0 || il >= TI || jl >= TJ) break;   // left the tile: load that one
+    // ---- the parent map: the code of every cell of the tile over its mask byte ----
+    asm volatile("; TSA_PARENTS begin");
+    {
+      const unsigned* col = s_tile + lane;   // image row r at col + r * BW: the cells il - 1, il, il + 1 of row jl = r - 1
+      unsigned* codes = reinterpret_cast<unsigned*>(s_mask) + lane * (TJ / 4);
+      unsigned a0 = col[0], a1 = col[1], a2 = col[2];                  // row jl - 1
+      unsigned c0 = col[BW], c1 = col[BW + 1], c2 = col[BW + 2];       // row jl
+#pragma unroll 1
+      for (int g = 0; g < TJ / 4; ++g) {   // four rows a turn: one word of masks in, one word of codes out
+        const unsigned m4 = codes[g];
+        unsigned out = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const unsigned* nx = col + (g * 4 + b + 2) * BW;
+          const unsigned e0 = nx[0], e1 = nx[1], e2 = nx[2];           // row jl + 1
+          out |= tsa_parent_code(c1, m4 >> (8 * b), a0, a1, a2, c0, c2, e0, e1, e2) << (8 * b);
+          a0 = c0; a1 = c1; a2 = c2;
+          c0 = e0; c1 = e1; c2 = e2;
+        }
+        codes[g] = out;
+      }
     }
-  }
-  if (!ok) {
-    if (lane == 0) A.results[q] = rna_astar_result{1, 0, INF, r.expanded, r.rounds, r.buckets};
-    return;
+    asm volatile("; TSA_PARENTS end");
+    // The cell of the start gets a code of its own, so that a step asks one question: go on (a move, 0..7) or not.  (The start
+    // ends the walk whatever its field word says, as it did when the walk tested it first at every cell.)
+    if (ti == start_ti && tj == start_tj && lane == (si & (TI - 1))) s_mask[lane * TJ + (sj & (TJ - 1))] = (unsigned char)TSA_CODE_START;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    // ---- walk inside the tile ----
+    int pos = (ci & (TI - 1)) + ((cj & (TJ - 1)) << 8);
+    int adr = (ci & (TI - 1)) * TJ + (cj & (TJ - 1));
+    asm volatile("" : "+v"(adr));   // (kept in a vector register, where the LDS read wants it: stepped by one v_add, not a scalar add and a copy)
+    int code;
+    for (;;) {   // ONE way out, below: several would be joined by the compiler through a variable that every step sets and tests
+      asm volatile("; TSA_STEP begin");
+      cells = tsa_writelane(lin, sel, cells);
+      ++len;
+      sel = len & 63;
+      code = __builtin_amdgcn_readfirstlane((int)s_mask[adr]);
+      if (__builtin_expect(sel == 0, 0)) {   // 64 cells are parked: out they go
+        // (all 64 or none, a wave-uniform test: a path that has outgrown rev ends as status 3 or 1, and neither reads rev)
+        if (len <= A.rev_cap) rev[len - 64 + lane] = cells;
+        // a field that leads in circles (no valid one does) never comes to the start: looked for here, once in 64 steps, it still ends
+        if (len > ncell) code = (int)TSA_PARENT_NONE;
+      }
+      if (code >= (int)TSA_PARENT_NONE) break;
+      // (code is wave-uniform: three v_readlane, no trip through the LDS crossbar)
+      lin += __builtin_amdgcn_readlane(step_lin, code);
+      pos += __builtin_amdgcn_readlane(step_pos, code);
+      adr += __builtin_amdgcn_readlane(step_adr, code);
+      // il = -1 or 64 shows in bit 6 of il + 256 jl, jl = -1 or 16 (with il inside) in bit 12
+      if (pos & 0x1040) break;   // left the tile: load that one
+      asm volatile("; TSA_STEP end");
+    }
+    asm volatile("" : "+s"(code));   // (asked again, not remembered per way out: see the loop)
+    if (code >= (int)TSA_PARENT_NONE) {
+      if (code == (int)TSA_CODE_START) break;
+      if (lane == 0) A.results[q] = rna_astar_result{1, 0, INF, r.expanded, r.rounds, r.buckets};
+      return;
+    }
+    // (pos + 257 = (il + 1) + 256 (jl + 1), both fields >= 0 also one cell outside the tile)
+    ci = (ti << 6) + ((pos + 257) & 0xff) - 1;
+    cj = (tj << 4) + ((pos + 257) >> 8) - 1;
   }
   if (len > A.max_path_len || len > A.rev_cap) {
     if (lane == 0) A.results[q] = rna_astar_result{3, len, r.cost, r.expanded, r.rounds, r.buckets};
     return;
   }
+  if (lane < (len & 63)) rev[(len & ~63) + lane] = cells;   // the tail (len <= rev_cap here)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
   int32_t* path = A.paths + (size_t)q * A.max_path_len;
@@ -1685,14 +1741,14 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
 // per workgroup.  Wavefront w of workgroup g serves the query at position P g + w of the batch's launch order (longest expected
 // search first, so one workgroup's paths are of similar length); it walks where the search left "found, path pending" and leaves
 // every other record alone (statuses 1, 2, 4 and 5 are final as the search kernel wrote them; a 5 is answered by the retry pass).
-// The walk is ONE chain of dependent instructions (a step: two LDS reads, a ballot, a lane read, a handful of scalar
-// instructions).  Inside the search kernel it was run by the workgroup's first wavefront while the workgroup's 37.6 KB of LDS and
-// its place on the CU stayed taken and the seven wave slots the other wavefronts had given back stood empty, since a new search
-// workgroup needs all eight at once: at the priority of the search wavefronts it shared its SIMD with, a step took 0.88 us and a
-// path of 2 000 cells 2 ms -- 18 % of the workgroup's residence (profiles/r05_search_job_stats.txt) --, at the highest issue
-// priority, where it gets its instructions in when it asks, 1.05 ms.  Here eight walks fill the eight wave slots of one search
-// workgroup (two wavefronts per SIMD at <= 64 VGPRs), and their eight images fit the LDS beside three resident search workgroups
-// (tests/test_astar_trace_kernel_host.py).
+// The walk is ONE chain of dependent instructions, so it is kept short: per tile the whole wavefront works out every cell's
+// parent at once, and a step is then a byte read, three lane reads and a dozen scalar instructions (tsa_backtrace_wave).
+// Inside the search kernel the walk was run by the workgroup's first wavefront while the workgroup's 37.6 KB of LDS and its
+// place on the CU stayed taken and the seven wave slots the other wavefronts had given back stood empty, since a new search
+// workgroup needs all eight at once.  Here eight walks fill the eight wave slots of one search workgroup (two wavefronts
+// per SIMD at <= 64 VGPRs), and their eight images fit the LDS beside three resident search workgroups
+// (tests/test_astar_trace_kernel_host.py).  They run at the highest issue priority: a walk gets its instructions in when it
+// asks, and the place it holds comes back sooner (profiles/r05_ab_backtrace_priority.txt, profiles/astar_trace_parents.txt).
 constexpr int TSA_TRACE_PATHS = 8;
 __global__ void __launch_bounds__(TSA_TRACE_PATHS * 64) __attribute__((amdgpu_waves_per_eu(TSA_WAVES_PER_EU, TSA_WAVES_PER_EU))) tsa_trace_kernel(const TsaLaunch A) {
   extern __shared__ __attribute__((aligned(16))) unsigned s_image[];   // TSA_TRACE_PATHS images of TSA_TRACE_IMAGE_WORDS, sized by the launch

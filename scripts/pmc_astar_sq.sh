@@ -28,10 +28,25 @@ for k, d in acc.items():
         for c, v in sorted(d.items()):
             print("   %-28s launches=%d avg=%.6g" % (c, len(v), sum(v) / len(v)))
 PY
+# the settled cells come next: bench.py reads the search kernel's block up to there.  The trace kernel's block follows as comments.
 # the settled cells of the batch the counters belong to (scripts/astar_stats.py prints mean and maximum per query)
 python3 - <<PY >> $OUT/summary.txt
 import re
 m = re.search(r"settled mean/max=(\d+)/", open("$OUT/log1.txt").read())
 if m: print("   %-28s %d  (256 queries x the mean the same run reports)" % ("SETTLED_CELLS_OF_THE_BATCH", int(m.group(1)) * 256))
+PY
+python3 - <<PY >> $OUT/summary.txt
+import csv, glob, collections
+acc = collections.defaultdict(lambda: collections.defaultdict(list))
+for f in glob.glob("$OUT/p*/**/*counter_collection.csv", recursive=True):
+    for r in csv.DictReader(open(f)):
+        k = r["Kernel_Name"].split("(")[0][-40:]
+        acc[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
+for k, d in acc.items():
+    if "trace" in k:
+        print("# the same passes, the trace kernel behind that search kernel (walks the batch's paths; not part of the figures bench.py quotes from the block above)")
+        print("# " + k)
+        for c, v in sorted(d.items()):
+            print("#   %-28s launches=%d avg=%.6g" % (c, len(v), sum(v) / len(v)))
 PY
 cat $OUT/summary.txt
