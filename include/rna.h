@@ -718,7 +718,15 @@ int rna_scan_match_pose(const rna_geometry* g, double x, double y, double yaw, d
 
 /* ---- global planning: waypoint-graph A* (the reference's own AStarPlanner) ------------------- */
 /* AStarPlanner::init + makePlan over a caller-supplied graph (astar_planner.cpp:63-145): start and
- * target positions are snapped to the closest vertex; path = start, vertex locations..., target. */
+ * target positions are snapped to the closest vertex; path = start, vertex locations..., target.
+ * 1 <= n_vertices <= 256, edge ends in [0, n_vertices), max_len >= 3; path_len[q] is the number of positions of the route
+ * (0 = no route); a row of paths_xy is written only when path_len[q] <= max_len and is otherwise left as the caller had it.
+ * A NEGATIVE EDGE WEIGHT IS REFUSED (RNA_EINVAL, nothing is launched).  Boost refuses it too: astar_bfs_visitor::examine_edge
+ * throws negative_edge.  On an undirected edge it is a negative cycle: relax() lowers the distance of either end in turn and
+ * re-opens both, until float absorption stops it -- 2^24 + 2 pops, each with one relaxation and one re-opening, in the CPU
+ * restatement (oracle/astar.c, counted by tests/test_graph_astar_host.py) for two vertices joined by an edge of weight -1 and
+ * a goal that is not connected: that would be one lane's work.  -0.0 and NaN pass: a NaN weight never relaxes, here and in
+ * Boost alike.  RNA_EINVAL as well for any other argument out of the ranges above; n = 0 is RNA_OK. */
 int rna_graph_astar_batch(rna_engine* e, int n_vertices, const double* vertex_xy, int n_edges,
                           const int32_t* edge_uv, const float* edge_weight /* NULL = 0 as the reference */,
                           const double* start_target_xy /* n*4 */, int n, double* paths_xy /* n*max_len*2 */,

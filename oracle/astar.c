@@ -18,7 +18,9 @@
  * (2) Waypoint-graph A*: restates boost::astar_search (Boost.Graph 1.54, the version ROS Indigo
  *     ships; NOT vendored under /root/reference) as called at mc/src/astar_planner.cpp:72-77:
  *     4-ary indirect heap keyed on f = d + h, BFS colouring, relax() with the undirected branch,
- *     visitor throwing at examine_vertex(goal).  "parity unpinned" (no reference test, Boost absent).
+ *     visitor throwing at examine_vertex(goal).  "parity unpinned" (no reference test, Boost absent);
+ *     shortest-route property pinned by tests/test_graph_astar_host.py where the heuristic is admissible
+ *     (against a plain float64 Dijkstra, route cost equal).  Boost itself is still absent.
  */
 #include "rna_oracle.h"
 
@@ -302,6 +304,13 @@ int og_graph_closest_vertex(int nv, const double* loc, const double pos[2]) {
   return best;
 }
 
+/* measurement aid (tests/test_graph_astar_host.py's premises): what the calling thread's og_graph_astar calls have done since
+ * the counters were last read -- whether a set of test inputs reaches the branches a wrong kernel would differ in */
+static __thread int64_t og_graph_count[OG_GRAPH_COUNTERS];
+void og_graph_astar_counters(int64_t* out) {
+  for (int k = 0; k < OG_GRAPH_COUNTERS; ++k) { out[k] = og_graph_count[k]; og_graph_count[k] = 0; }
+}
+
 int og_graph_astar(int nv, const double* loc, int ne, const int* euv, const float* ew, int start,
                    int goal, int* path, int cap) {
   /* out-edge lists in add_edge order (adjacency_list<listS, vecS, undirectedS>) */
@@ -334,13 +343,16 @@ int og_graph_astar(int nv, const double* loc, int ne, const int* euv, const floa
   int found = 0;
   while (h.n) {
     int u = h.data[0];
+    if (h.n > og_graph_count[OG_GRAPH_MAX_HEAP]) og_graph_count[OG_GRAPH_MAX_HEAP] = h.n;
     dheap_pop(&h);
+    og_graph_count[OG_GRAPH_POPS]++;
     if (u == goal) { found = 1; break; } /* examine_vertex -> throw found_goal */
     for (int k = off[u]; k < off[u + 1]; ++k) {
       int v = adj_v[k];
       float w = adj_w[k];
       /* relax(), boost/graph/relax.hpp (closed_plus, std::less) incl. the undirected branch */
       int decreased = 0;
+      og_graph_count[OG_GRAPH_RELAXATIONS]++;
       float d_u = d[u], d_v = d[v];
       float cand = (d_u == FLT_MAX || w == FLT_MAX) ? FLT_MAX : d_u + w;
       if (cand < d_v) {
@@ -348,16 +360,16 @@ int og_graph_astar(int nv, const double* loc, int ne, const int* euv, const floa
         if (d[v] < d_v) { p[v] = u; decreased = 1; }
       } else {
         float cand2 = (d_v == FLT_MAX || w == FLT_MAX) ? FLT_MAX : d_v + w;
-        if (cand2 < d_u) { d[u] = cand2; if (d[u] < d_u) { p[u] = v; decreased = 1; } }
+        if (cand2 < d_u) { d[u] = cand2; if (d[u] < d_u) { p[u] = v; decreased = 1; og_graph_count[OG_GRAPH_UNDIRECTED]++; } }
       }
       if (color[v] == 0) {
         if (decreased) f[v] = (d[v] == FLT_MAX) ? FLT_MAX : d[v] + HEUR(v);
         color[v] = 1;
         dheap_push(&h, v);
       } else if (color[v] == 1) {
-        if (decreased) { f[v] = (d[v] == FLT_MAX) ? FLT_MAX : d[v] + HEUR(v); dheap_up(&h, h.index_in_heap[v]); }
+        if (decreased) { f[v] = (d[v] == FLT_MAX) ? FLT_MAX : d[v] + HEUR(v); dheap_up(&h, h.index_in_heap[v]); og_graph_count[OG_GRAPH_GRAY_DECREASED]++; }
       } else {
-        if (decreased) { f[v] = (d[v] == FLT_MAX) ? FLT_MAX : d[v] + HEUR(v); dheap_push(&h, v); color[v] = 1; }
+        if (decreased) { f[v] = (d[v] == FLT_MAX) ? FLT_MAX : d[v] + HEUR(v); dheap_push(&h, v); color[v] = 1; og_graph_count[OG_GRAPH_BLACK_REOPENED]++; }
       }
     }
     color[u] = 2;

@@ -194,6 +194,17 @@ void og_astar_query_on_map(const og_geom* g, const float* master, int start_lin,
 int og_graph_astar(int n_vertices, const double* loc_xy, int n_edges, const int* edge_uv,
                    const float* edge_w, int start, int goal, int* path_vertices, int cap);
 int og_graph_closest_vertex(int n_vertices, const double* loc_xy, const double pos[2]);
+/* what the calling thread's og_graph_astar calls did since the last read (a measurement aid); reading zeroes the counters */
+enum {
+  OG_GRAPH_UNDIRECTED = 0,     /* relaxations that lowered d[u] through the undirected branch of relax() */
+  OG_GRAPH_BLACK_REOPENED,     /* black vertices put back on the heap */
+  OG_GRAPH_GRAY_DECREASED,     /* decrease-keys on a gray vertex */
+  OG_GRAPH_MAX_HEAP,           /* the largest heap size at a pop */
+  OG_GRAPH_POPS,               /* vertices taken off the heap */
+  OG_GRAPH_RELAXATIONS,        /* out-edges examined */
+  OG_GRAPH_COUNTERS
+};
+void og_graph_astar_counters(int64_t* out /* OG_GRAPH_COUNTERS */);
 /* The reference's hard-coded graph (astar_planner.cpp:98-127) and makePlan() path shape. */
 int og_reference_graph(double* loc_xy /*18*/, int* edge_uv /*20*/);
 int og_graph_make_plan(const double start[2], const double target[2], double* path_xy, int cap);

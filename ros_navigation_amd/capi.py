@@ -1086,7 +1086,9 @@ class Engine:
         v = np.ascontiguousarray(vertex_xy, dtype=np.float64).reshape(-1, 2)
         e = np.ascontiguousarray(edge_uv, dtype=np.int32).reshape(-1, 2)
         st = np.ascontiguousarray(start_target, dtype=np.float64).reshape(-1, 4)
-        w = None if edge_weight is None else np.ascontiguousarray(edge_weight, dtype=np.float32)
+        w = None if edge_weight is None else np.ascontiguousarray(edge_weight, dtype=np.float32).reshape(-1)
+        if w is not None and len(w) != len(e):      # the library reads one weight per edge
+            raise ValueError("graph_astar: %d edge weights for %d edges" % (len(w), len(e)))
         n = len(st)
         max_len = max_len or (len(v) + 2)
         paths = np.zeros((n, max_len, 2), np.float64)

@@ -359,6 +359,13 @@ class Staging {
     if (n) downloads_.push_back(Download{host, d, n * sizeof(T)});
     return d;
   }
+  // in() and out() on one buffer: what the kernel does not write comes back as the caller had it
+  template <typename T>
+  T* inout(T* host, size_t n) {
+    T* d = in(host, n);
+    if (d && n) downloads_.push_back(Download{host, d, n * sizeof(T)});
+    return d;
+  }
   // The launch check, the registered downloads, the stream synchronisation.  A call that staged nothing (the _device form
   // of an entry point that has both) stops after the launch check: it has no temporaries to outlive.
   int finish() {

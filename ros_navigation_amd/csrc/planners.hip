@@ -653,6 +653,11 @@ extern "C" int rna_graph_astar_batch(rna_engine* e, int nv, const double* vertex
   if (n == 0) return RNA_OK;
   for (int k = 0; k < 2 * ne; ++k)
     if (edge_uv[k] < 0 || edge_uv[k] >= nv) return RNA_EINVAL;
+  // a negative weight on an undirected edge is a negative cycle: relax() would lower both ends in turn and re-open them until
+  // float absorption ends it (include/rna.h).  -0.0 and NaN pass: NaN compares false and never relaxes.
+  if (edge_weight)
+    for (int k = 0; k < ne; ++k)
+      if (edge_weight[k] < 0) return RNA_EINVAL;
   RNA_ENTER(e);
   // out-edge lists in add_edge order: add_edge(u,v) appends to u's list and to v's list
   std::vector<int> off(nv + 1, 0), fill(nv, 0), adj_v(2 * ne + 1);
@@ -671,7 +676,9 @@ extern "C" int rna_graph_astar_batch(rna_engine* e, int nv, const double* vertex
   const double* d_st = st.in(start_target_xy, (size_t)4 * n);
   float* d_sf = st.scratch<float>((size_t)2 * nv * n);
   int* d_si = st.scratch<int>((size_t)4 * nv * n);
-  double* d_paths = st.out(paths_xy, (size_t)2 * max_len * n);
+  // the kernel writes a row only up to its route's length, and not at all when the route does not fit or does not exist: the
+  // rest comes back as the caller had it (include/rna.h), not as whatever the device allocation held
+  double* d_paths = st.inout(paths_xy, (size_t)2 * max_len * n);
   int* d_len = st.out(path_len, (size_t)n);
   if (st.ok())
     hipLaunchKernelGGL(graph_astar_kernel, dim3((n + 63) / 64), dim3(64), 0, e->stream, G, d_st, n, d_sf, d_si, d_paths, max_len, d_len);

@@ -142,6 +142,8 @@ def lib():
         L.og_astar_query_on_map.restype = None
         L.og_graph_astar.argtypes = [C.c_int, d2, C.c_int, i2, fp, C.c_int, C.c_int, i2, C.c_int]
         L.og_graph_closest_vertex.argtypes = [C.c_int, d2, d2]
+        L.og_graph_astar_counters.argtypes = [C.POINTER(C.c_int64)]
+        L.og_graph_astar_counters.restype = None
         L.og_reference_graph.argtypes = [d2, i2]
         L.og_graph_make_plan.argtypes = [d2, d2, d2, C.c_int]
         L.og_srand.argtypes = [C.POINTER(RandState), C.c_uint]
@@ -464,6 +466,16 @@ def astar_last_settled_at_goal():
     f = lib().og_astar_last_settled_at_goal
     f.restype = C.c_int32
     return int(f())
+
+
+GRAPH_COUNTERS = ("undirected", "black_reopened", "gray_decreased", "max_heap", "pops", "relaxations")   # rna_oracle.h's enum
+
+
+def graph_astar_counters():
+    """what the calling thread's og_graph_astar calls did since the last read, by name; reading zeroes the counters"""
+    out = (C.c_int64 * len(GRAPH_COUNTERS))()
+    lib().og_graph_astar_counters(out)
+    return dict(zip(GRAPH_COUNTERS, (int(v) for v in out)))
 
 
 def astar_query_on_map(g, master, start, goal, path_cap=None):
