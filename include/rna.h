@@ -751,7 +751,13 @@ int rna_rrt_batch_device(rna_engine* e, const rna_rrt_query* queries_device, int
  * beams of the scan that is projected -- the decimated one when angle_increment < 0.017 (rna_scan_projected_beams).
  * Every beam is transformed with the pose interpolated for its index (position linearly, yaw along the shortest arc),
  * as transformLaserScanToPointCloud does with tf's start / end transforms.  End pose == start pose: a pose that is
- * constant over the scan. */
+ * constant over the scan.
+ * The arithmetic, all in double, each operation rounded on its own (tests/_scan_reference.py replays it): beam i of n projected
+ * beams has ratio = i * (1 / (n - 1)), 0 for n = 1; its point is (float)(range * cos(a)), (float)(range * sin(a)) with
+ * a = angle_min + i * angle_increment (the decimated scan's increment); dyaw = fmod(yaw_end - yaw, 2 pi), less 2 pi if above
+ * pi, then plus 2 pi if below -pi; yaw_i = yaw + ratio * dyaw; t = (1 - ratio) * start + ratio * end per coordinate; end point
+ * (float)((cos(yaw_i) * px - sin(yaw_i) * py) + tx), (float)((sin(yaw_i) * px + cos(yaw_i) * py) + ty).  A scan of no range
+ * gives no ray. */
 typedef struct {
   float angle_min, angle_max, angle_increment, range_min, range_max;
   int32_t n_ranges;

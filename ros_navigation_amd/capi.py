@@ -1135,6 +1135,15 @@ class Engine:
                                                 C.byref(n)))
         return rays[:n.value]
 
+    def scan_to_rays_device(self, scans_ptr, n_scans, ranges_ptr, max_beams_per_scan, rays_ptr, max_rays, n_rays_ptr):
+        """scan_to_rays on device buffers: the count stays on the device (the required count, where it exceeds max_rays)."""
+        self._check(self._L.rna_scan_to_rays_device(self.h, scans_ptr, n_scans, ranges_ptr, max_beams_per_scan, rays_ptr, max_rays,
+                                                    n_rays_ptr))
+
+    def scan_to_rays_tf_device(self, scans_ptr, n_scans, ranges_ptr, max_beams_per_scan, rays_ptr, max_rays, n_rays_ptr):
+        self._check(self._L.rna_scan_to_rays_tf_device(self.h, scans_ptr, n_scans, ranges_ptr, max_beams_per_scan, rays_ptr, max_rays,
+                                                       n_rays_ptr))
+
     def to_occupancy_grid(self, layer, data_min=0.0, data_max=255.0):
         """GridMapRosConverter::toOccupancyGrid: int8[rows*cols] in nav_msgs/OccupancyGrid order."""
         g = self.geometry()

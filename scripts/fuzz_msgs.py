@@ -1,8 +1,10 @@
 """Developer tool: time-boxed random parity run of the message-side kernels against the oracle: toOccupancyGrid /
 fromOccupancyGrid (random geometry, layer contents incl. NaN / out-of-range / +-inf, data ranges, moved buffers),
-LaserScan -> rays (random beam counts, increments either side of the 0.017 rad decimation threshold, ranges at and
-beyond range_min / range_max, NaN / inf returns).  usage: python scripts/fuzz_msgs.py [seconds] [seed]"""
+LaserScan -> rays (batches of scans that differ in beam count and increment, either side of the 0.017 rad decimation threshold,
+at offsets with gaps, ranges at and beyond range_min / range_max, NaN / inf returns; host and device forms), every end point
+held to the accepted-value rule of tests/_scan_reference.py.  usage: python scripts/fuzz_msgs.py [seconds] [seed]"""
 import ctypes as C
+import math
 import os
 import sys
 import time
@@ -15,13 +17,16 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 import ros_navigation_amd as R  # noqa: E402
 import _oracle as O  # noqa: E402
+import _scan_reference as SR  # noqa: E402
+from _gpu import SENTINEL, device_libm_error, scan_device_form  # noqa: E402
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 torch.zeros(1, device="cuda")
 rng = np.random.default_rng(seed)
 t_end = time.time() + budget
-cases = cells = nrays = inexact = 0
+cases = cells = nrays = inexact = two_valued = device_forms = 0
+K, worst = 2, 0.0    # K_device: 1 ulp of margin over the measured error of the device libm, raised where a batch measures more
 while time.time() < t_end:
     res = float(rng.choice([0.05, 0.1, 0.2, 0.025]))
     lx, ly = float(rng.uniform(2, 20)), float(rng.uniform(2, 20))
@@ -59,41 +64,62 @@ while time.time() < t_end:
         if not (np.array_equal(np.isnan(got), np.isnan(want)) and np.array_equal(got[~np.isnan(got)], want[~np.isnan(want)])):
             print("MISMATCH from_occupancy", here)
             sys.exit(1)
-    # laser scans
-    ns, beams = int(rng.integers(1, 12)), int(rng.choice([1, 2, 37, 181, 361, 1081, 2500]))
-    inc = np.float32(rng.choice([0.0005, 0.004, 0.0169, 0.017, 0.0171, 0.05, 1.5 * np.pi / max(beams, 1)]))
-    scans, ranges = R.synth.laser_scans(ns, beams, lx, ly, seed=int(rng.integers(0, 1 << 30)), angle_increment=inc)
-    ranges[rng.random(len(ranges)) < 0.05] = np.float32(rng.choice([np.nan, np.inf, 0.0, -1.0]))
-    k = rng.random(len(ranges))
-    per_scan_max = np.repeat(scans["range_max"], scans["n_ranges"])[: len(ranges)]
-    per_scan_min = np.repeat(scans["range_min"], scans["n_ranges"])[: len(ranges)]
-    ranges[k < 0.05] = per_scan_max[k < 0.05]
-    ranges[(k > 0.05) & (k < 0.1)] = per_scan_min[(k > 0.05) & (k < 0.1)]
-    want = O.scan_to_rays(scans, ranges)
-    got = e.scan_to_rays(scans, ranges)
-    ok = (len(got) == len(want) and np.array_equal(got["sx"], want["sx"]) and np.array_equal(got["sy"], want["sy"]) and
-          np.array_equal(got["clear_end"], want["clear_end"]) and np.allclose(got["ex"], want["ex"], rtol=0, atol=1e-6) and
-          np.allclose(got["ey"], want["ey"], rtol=0, atol=1e-6))
-    if not ok:
-        print("MISMATCH scan_to_rays", here, dict(ns=ns, beams=beams, inc=float(inc)), len(got), len(want))
-        sys.exit(1)
-    nrays += len(want)
-    inexact += int(((got["ex"] != want["ex"]) | (got["ey"] != want["ey"])).sum())
-    # the same with full sensor transforms (tilted / rolled / raised mounts, end quaternions of either sign)
-    scans_tf, ranges_tf = R.synth.laser_scans_tf(ns, beams, lx, ly, seed=int(rng.integers(0, 1 << 30)), angle_increment=inc,
-                                                 tilt=float(rng.choice([0.05, 0.35, 1.2])), planar=float(rng.choice([0.0, 0.25, 1.0])))
-    ranges_tf[rng.random(len(ranges_tf)) < 0.05] = np.float32(rng.choice([np.nan, np.inf, 0.0, -1.0]))
-    want = O.scan_to_rays_tf(scans_tf, ranges_tf)
-    got = e.scan_to_rays_tf(scans_tf, ranges_tf)
-    ok = (len(got) == len(want) and np.array_equal(got["sx"], want["sx"]) and np.array_equal(got["sy"], want["sy"]) and
-          np.array_equal(got["clear_end"], want["clear_end"]) and np.allclose(got["ex"], want["ex"], rtol=0, atol=1e-6) and
-          np.allclose(got["ey"], want["ey"], rtol=0, atol=1e-6))
-    if not ok:
-        print("MISMATCH scan_to_rays_tf", here, dict(ns=ns, beams=beams, inc=float(inc)), len(got), len(want))
-        sys.exit(1)
-    nrays += len(want)
-    inexact += int(((got["ex"] != want["ex"]) | (got["ey"] != want["ey"])).sum())
+    # laser scans: a batch of scans that differ in beam count and increment, their ranges at offsets with gaps and out of scan
+    # order; both pose forms; for half of the cases through the device form with a segment stride of its own
+    ns = int(rng.integers(1, 7))
+    for form, make in (("planar", R.synth.laser_scans), ("tf", R.synth.laser_scans_tf)):
+        parts, at = [], int(rng.integers(0, 9))
+        kw = dict(tilt=float(rng.choice([0.05, 0.35, 1.2])), planar=float(rng.choice([0.0, 0.25, 1.0]))) if form == "tf" else {}
+        for k in rng.permutation(ns):
+            beams = int(rng.choice([0, 1, 2, 37, 181, 257, 361, 1081, 2500]))
+            inc = np.float32(rng.choice([0.0005, 0.004, 0.0169, 0.017, 0.0171, 0.05, 1.5 * np.pi / max(beams, 1)]))
+            if beams > 400 and not inc < 0.017:
+                beams = 400                           # the reference's mpmath calls are what a beam costs
+            sc, r = make(1, beams, lx, ly, seed=int(rng.integers(0, 1 << 30)), angle_increment=inc, **kw)
+            r[rng.random(len(r)) < 0.05] = np.float32(rng.choice([np.nan, np.inf, 0.0, -1.0]))
+            u = rng.random(len(r))
+            r[u < 0.05] = sc["range_max"][0]
+            r[(u > 0.05) & (u < 0.1)] = sc["range_min"][0]
+            sc["ranges_offset"] = at
+            parts.append((int(k), sc, r, at))
+            at += beams + int(rng.integers(0, 50))
+        ranges = np.full(at + 1, 3.25, np.float32)
+        for _, _, r, off in parts:
+            ranges[off:off + len(r)] = r
+        scans = np.concatenate([sc for _, sc, _, _ in sorted(parts, key=lambda p: p[0])])
+        here_s = dict(form=form, n_ranges=scans["n_ranges"].tolist(), inc=[float(v) for v in scans["angle_increment"]])
+        if rng.random() < 0.5:
+            total, stride = int(scans["n_ranges"].sum()) + 1, int(rng.integers(max(1, int(scans["n_ranges"].max())), 8193))
+            n, raw = scan_device_form(e, form, scans, ranges, stride, total)
+            got = raw[:min(n, total) * 40].view(R.capi.RAY_DTYPE).copy()
+            here_s["device_stride"] = stride
+            if n > total or not (raw[n * 40:] == SENTINEL).all():
+                print("MISMATCH scan_to_rays device form", here, here_s, n)
+                sys.exit(1)
+            device_forms += 1
+        else:
+            got = (e.scan_to_rays if form == "planar" else e.scan_to_rays_tf)(scans, ranges)
+        # the shared accepted-set rule (tests/_scan_reference.py); K from the device libm's error over this batch's own arguments
+        while True:
+            libm = SR.Libm(K)
+            ref = SR.Batch(form, scans, ranges, libm)
+            err = device_libm_error({fn: sorted(a) for fn, a in libm.asked.items()})
+            worst = max([worst] + list(err.values()))
+            need = math.ceil(max(list(err.values()) + [0.0])) + 1
+            if need <= K:
+                break
+            K = need
+        bad = ref.frame_mismatch(got)
+        out = ref.outside(got) if bad is None else []
+        if K > 4 or bad is not None or len(out):
+            print("MISMATCH scan_to_rays", here, here_s, dict(K=K, libm_error=err), bad, len(got), ref.n, out[:5], got[out[:5]])
+            sys.exit(1)
+        want = (O.scan_to_rays if form == "planar" else O.scan_to_rays_tf)(scans, ranges)
+        nrays += ref.n
+        inexact += int(((got["ex"] != want["ex"]) | (got["ey"] != want["ey"])).sum())
+        two_valued += ref.multi_valued()
     cases += 1
     e.close()
-print("msgs fuzz ok: %d maps, %d cells converted, %d rays from scans (%d end points differ by a float32 ulp) in %.0f s, seed %d"
-      % (cases, cells, nrays, inexact, budget, seed))
+print("msgs fuzz ok: %d maps, %d cells converted, %d rays from scans (%d batches through the device form; every end point an accepted "
+      "value with K = %d, device libm within %.3f ulp; %d end points differ from glibc's, %d beams had two accepted values) in %.0f s, seed %d"
+      % (cases, cells, nrays, device_forms, K, worst, inexact, two_valued, budget, seed))

@@ -127,3 +127,61 @@ def centre(g, lin):
 def engine_centre(e, lin):
     """position of buffer cell `lin`, asked of the ENGINE (rna_get_position): another source of truth than centre()"""
     return e.get_position(lin % e.rows, lin // e.rows)
+
+
+# ---- laser ingestion on device buffers ----
+SENTINEL = 0xA5
+
+
+def dev(a):
+    """a numpy array's bytes as a torch device tensor"""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).cuda()
+
+
+def scan_device_form(e, form, scans, ranges, stride, max_rays, room=None):
+    """rna_scan_to_rays_device (form "planar") / rna_scan_to_rays_tf_device ("tf") on torch tensors, the count between two
+    guard words: (the count the call left on the device, the whole rays buffer as bytes -- `room` rays and 64 bytes more, SENTINEL
+    where nothing was written)"""
+    import torch
+    d_scans, d_ranges = dev(scans), dev(ranges)
+    d_rays = torch.full(((max_rays if room is None else room) * O.RAY_DTYPE.itemsize + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
+    d_n = torch.full((3,), -7, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    fn = e.scan_to_rays_device if form == "planar" else e.scan_to_rays_tf_device
+    fn(d_scans.data_ptr(), len(scans), d_ranges.data_ptr(), stride, d_rays.data_ptr(), max_rays, d_n[1:].data_ptr())
+    e.synchronize()
+    n = d_n.cpu().numpy()
+    assert n[0] == -7 and n[2] == -7
+    return int(n[1]), d_rays.cpu().numpy()
+
+
+def device_libm_error(asked):
+    """largest error in ulps of torch.cos / sin / acos on float64 device tensors (the device math library, not a kernel of this
+    project) against mpmath, over the arguments `asked` = {name: set or array of doubles}"""
+    import torch
+    import _scan_reference as SR
+    return {fn: SR.ulp_error(fn, sorted(a), getattr(torch, fn)(torch.from_numpy(np.array(sorted(a), np.float64)).cuda()).cpu().numpy())
+            for fn, a in asked.items() if len(a)}
+
+
+def check_scan_rays(form, scans, ranges, rays, what=""):
+    """the accepted-value rule of tests/_scan_reference.py on the rays a scan entry point gave: count, order, origins and clear_end
+    equal the reference's, every ex / ey one of the float32 values it accepts with K_device = the device libm's error over THIS
+    batch's arguments, rounded up, plus 1 (above 4: a finding, not a value to adopt).  Returns (the reference Batch, K_device)."""
+    import math
+    import _scan_reference as SR
+    K = 2
+    while True:
+        libm = SR.Libm(K)
+        ref = SR.Batch(form, scans, ranges, libm)
+        err = device_libm_error(libm.asked)
+        need = math.ceil(max(err.values(), default=0.0)) + 1
+        assert need <= 4, (what, err)
+        if need <= K:
+            break
+        K = need
+    assert ref.frame_mismatch(rays) is None, (what, ref.frame_mismatch(rays))
+    out = ref.outside(rays)
+    assert len(out) == 0, (what, K, len(out), out[:5], rays[out[:5]])
+    return ref, K

@@ -5,7 +5,9 @@ moved once or twice (grid A*); random geometry / resolution / moved buffers, end
 map border, poses past the border, for half of the cases one of the VFH parameter sets of tests/_vfh_cases.py
 (map update + VFH+); resolutions 0.025-0.2 m, origins up to 2000 m, radii of k and k + 1/2
 cells, moved maps (robot radius); sequences of map operations on one engine against the model of tests/_mapmodel.py (map state);
-waypoint graphs of up to 256 vertices and batches of up to 200 queries, a quarter of them held to Dijkstra as well (graph A*).
+waypoint graphs of up to 256 vertices and batches of up to 200 queries, a quarter of them held to Dijkstra as well (graph A*);
+occupancy-grid conversions and LaserScan batches of unlike scans through the host and the device forms, every end point held to the
+accepted-value rule of tests/_scan_reference.py (messages).
 A fuzzer exits non-zero at the first difference from the oracle
 and prints the configuration that reproduces it.  The search kernel's correctness rests on an asynchronous scheduler,
 `asm volatile` fences and on what the optimiser may hoist: this net catches what the hand-picked cases do not."""
@@ -64,3 +66,14 @@ def test_fuzz_graph_fixed_seed():
     # graph also costs a launch and its staging.
     assert graphs >= 200, text
     assert int(text.split("(")[1].split("held to Dijkstra")[0]) >= 40, text
+
+
+def test_fuzz_msgs_fixed_seed():
+    text = run_fuzzer("fuzz_msgs.py", 10, 308)
+    maps = int(text.split("fuzz ok:")[1].split("maps")[0])
+    # What a case costs is the mpmath side of the scan reference (tests/_scan_reference.py) and the oracle's conversions.  Measured
+    # on a CPU-only machine with the engine's answers replaced by the oracle's own: 123 maps and 93 000 rays in 10 s with this
+    # seed (125 and 120 maps with seeds 1 and 2).  The floor is far below half of that: the GPU host's CPUs are shared, and there
+    # a map also costs an engine, its uploads and the launches.
+    assert maps >= 30, text
+    assert int(text.split("(")[1].split("batches through the device form")[0]) >= 10, text

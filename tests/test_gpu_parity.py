@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import _oracle as O
-from _gpu import Hip, R, bits, same_f32  # noqa: F401  (R: the fixture)
+from _gpu import Hip, R, bits, check_scan_rays, same_f32  # noqa: F401  (R: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -1011,6 +1011,7 @@ def test_scan_to_rays_matches_oracle_and_feeds_himm(R):
         assert np.array_equal(got["sx"], want["sx"]) and np.array_equal(got["sy"], want["sy"])
         assert np.array_equal(got["clear_end"], want["clear_end"])
         assert np.allclose(got["ex"], want["ex"], rtol=0, atol=1e-6) and np.allclose(got["ey"], want["ey"], rtol=0, atol=1e-6)
+        check_scan_rays("planar", scans, ranges, got, beams)         # ... and every end point is an accepted float32 value
         exact = (got["ex"] == want["ex"]) & (got["ey"] == want["ey"])
         assert exact.mean() > 0.99
         if inc is None:
@@ -1043,6 +1044,7 @@ def test_scan_to_rays_with_full_sensor_transforms_matches_oracle(R):
         assert np.array_equal(got["sx"], want["sx"]) and np.array_equal(got["sy"], want["sy"])
         assert np.array_equal(got["clear_end"], want["clear_end"])
         assert np.allclose(got["ex"], want["ex"], rtol=0, atol=1e-6) and np.allclose(got["ey"], want["ey"], rtol=0, atol=1e-6)
+        check_scan_rays("tf", scans, ranges, got, beams)             # ... and every end point is an accepted float32 value
         exact = (got["ex"] == want["ex"]) & (got["ey"] == want["ey"])
         assert exact.mean() > 0.99
     # planar poses, both entry points
@@ -1079,6 +1081,8 @@ def test_scan_with_tf_jitter_between_start_and_end_keeps_every_beam(R):
         assert np.isfinite(got[f]).all()
     assert np.array_equal(got["sx"], want["sx"]) and np.array_equal(got["clear_end"], want["clear_end"])
     assert np.allclose(got["ex"], want["ex"], rtol=0, atol=1e-6) and np.allclose(got["ey"], want["ey"], rtol=0, atol=1e-6)
+    check_scan_rays("tf", scans, ranges, got)
+    check_scan_rays("tf", still, ranges, const)
     assert np.allclose(got["ex"], const["ex"], rtol=0, atol=1e-5) and np.allclose(got["ey"], const["ey"], rtol=0, atol=1e-5)
     e.close()
 
