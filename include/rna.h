@@ -740,6 +740,24 @@ typedef struct {
   int32_t max_samples;         /* bound for extendTree's while(true) */
 } rna_rrt_query;
 typedef struct { int32_t status, path_len, tree_size, samples; } rna_rrt_result;
+/* RrtPlanner::makePlan for n queries on the master layer, one workgroup a query, each with its own rand() stream.
+ *   status     1  reached: the last node is within close_tolerance of the target or, for a target outside the map, of the
+ *                 map's border (ifFinishPlan);
+ *              0  the tree is full at its 2000 nodes (rrt_planner.cpp:6) without having reached; the path is the one from the
+ *                 last node, as makePlan returns it;
+ *             -1  the budget of max_samples draws of extendTree ran out: no path, path_len 0.  max_samples <= 0 is -1 at
+ *                 once, with tree_size 1 and samples 0 (unless the start itself finishes the plan: status 1, path_len 1).
+ *   tree_size  nodes in the tree, the start included; samples: draws of extendTree, blocked ones included.
+ *   Way points run goal -> start, as backtraceTree leaves them: row q of paths_xy (max_path_len x 2 doubles) holds the last
+ *   node first and the query's start last.
+ *   path_len is the FULL length of the path even when it exceeds max_path_len; only the first max_path_len way points
+ *   (the goal side) are then written.  A tree never holds more than 2000 nodes, so max_path_len = 2000 cuts nothing.
+ *   What the call does not write -- a row behind min(path_len, max_path_len) way points, the whole row of a query with
+ *   status -1 -- comes back as the caller had it, in both forms (the host form uploads the caller's rows first).
+ *   findNearNode's `shortest = 9999.0` is kept: a sample 9999 m or more from every node extends node 0, the start.
+ * RNA_EINVAL for max_path_len <= 0, n < 0 or a null pointer with n > 0, before anything is launched; n = 0 is RNA_OK and
+ * touches nothing.  Starts are expected inside the map; close_tolerance and the positions finite.  The _device form is
+ * asynchronous on the engine stream. */
 int rna_rrt_batch(rna_engine* e, const rna_rrt_query* queries_host, int n, double* paths_xy_host,
                   int max_path_len, rna_rrt_result* results_host);
 int rna_rrt_batch_device(rna_engine* e, const rna_rrt_query* queries_device, int n, double* paths_xy_device,

@@ -1098,11 +1098,15 @@ class Engine:
                                                   max_len, _ptr(plen)))
         return plen, paths
 
-    def rrt(self, queries, max_path_len=2048):
+    def rrt(self, queries, max_path_len=2048, paths=None):
+        """paths: the caller's own (n, max_path_len, 2) float64 array instead of a zeroed one -- what the call does not write
+        (include/rna.h) stays as it was"""
         assert queries.dtype == RRT_QUERY_DTYPE
         queries = np.ascontiguousarray(queries)
         n = len(queries)
-        paths = np.zeros((n, max_path_len, 2), np.float64)
+        if paths is None:
+            paths = np.zeros((n, max_path_len, 2), np.float64)
+        assert paths.dtype == np.float64 and paths.shape == (n, max_path_len, 2) and paths.flags["C_CONTIGUOUS"]
         res = np.zeros(n, RRT_RESULT_DTYPE)
         self._check(self._L.rna_rrt_batch(self.h, _ptr(queries), n, _ptr(paths), max_path_len, _ptr(res)))
         return res, paths

@@ -389,8 +389,10 @@ __device__ __forceinline__ RrtEval rrt_evaluate(const Geom& g, const float* __re
   // 2^-48, and exactly those are re-examined with glibc_hypot in the reference's order.
   // One pass: every lane keeps its nearest node by squared distance (lowest index among equals) and
   // its second-smallest squared distance.  After the wave reduction, hypot is evaluated for at most one
-  // node per lane; only if some lane holds TWO nodes inside the 2^-46 band (practically never) the
-  // band is rescanned in full.
+  // node per lane; only if some lane holds TWO nodes inside the 2^-46 band the band is rescanned in full.  That is
+  // no rare path: starts and samples are cell centres, so on a tree that still sits on the lattice equal distances
+  // are common -- every fourth sample of the 10 m RRT test of tests/test_gpu_parity.py (9111 of 36 000) and every
+  // fourth of case A of tests/_rrt_cases.py takes it, which is why it is well tested.
   double l1 = 1.0e300, l2 = 1.0e300;
   int i1 = 0x7fffffff;
   for (int i0 = lane; i0 < n_tree; i0 += 256) {   // four nodes per lane and trip: the LDS reads go out together
@@ -453,7 +455,7 @@ __device__ __forceinline__ RrtEval rrt_evaluate(const Geom& g, const float* __re
     // wavefronts per query instead of eight fit the chip).  Against glibc's atan2 / cos / sin the offset differs in
     // its last bits either way (the device libm's does too, DESIGN.md 4 "What stays open"): the sum with the node's
     // coordinate then rounds differently for a few per cent of the nodes, by one ulp, which only matters at the
-    // last-bit ties scripts/fuzz_rrt.py classifies.
+    // last-bit ties of DESIGN.md 4 (against oracle/rrt.c in THIS formulation the kernel is exact: tests/test_gpu_rrt.py).
     const double sdx = rx - npx, sdy = ry - npy;
     const double sh = sqrt(sdx * sdx + sdy * sdy);
     wx = npx + strideStep * (sdx / sh);
@@ -729,7 +731,9 @@ extern "C" int rna_rrt_batch(rna_engine* e, const rna_rrt_query* queries_host, i
   Staging st(e, "rna_rrt_batch");
   const rna_rrt_query* dq = st.in(queries_host, (size_t)n);
   rna_rrt_result* dr = st.out(results_host, (size_t)n);
-  double* dp = st.out(paths_xy_host, (size_t)n * max_path_len * 2);
+  // the kernel writes a row only up to min(path_len, max_path_len), and not at all for a query that ran out of its budget: the
+  // rest comes back as the caller had it (include/rna.h), not as whatever the device allocation held
+  double* dp = st.inout(paths_xy_host, (size_t)n * max_path_len * 2);
   int* tp = st.scratch<int>((size_t)n * RRT_ITER);
   if (!st.ok()) return st.finish();
   const int rc = rrt_launch(e, dq, n, dp, max_path_len, dr, tp);

@@ -1,6 +1,8 @@
-"""Developer tool: time-boxed random parity run of rrt_kernel against the CPU oracle (status, tree size, sample count,
-path length exact; way points at 1e-9 m) over random map sizes, resolutions, obstacle densities, moved maps
-(circular-buffer start != 0), targets inside / outside the map, seeds and sample budgets.
+"""Developer tool: time-boxed random parity run of rrt_kernel against the CPU oracle in the kernel's formulation of the steering
+step (oracle/rrt.c, steer = 1: status, tree size, sample count, path length and every way point bit for bit, and every element
+of the paths array the call may not write still the caller's) over random map sizes, resolutions, obstacle densities, moved
+maps (circular-buffer start != 0), targets inside / outside the map, seeds and sample budgets; a share of the cases through the
+device form, a share with max_path_len below the paths.  Exits 1 at the first difference of any kind.
 usage: python scripts/fuzz_rrt.py [seconds] [seed]
        python scripts/fuzz_rrt.py repro <seed> <case> <query>    # first diverging sample of a reported mismatch"""
 import ctypes as C
@@ -47,7 +49,10 @@ def gen_case(rng):
     q["close_tolerance"] = rng.choice([0.2, 0.05, 0.5], nq)
     q["seed"] = rng.integers(0, 1 << 32, nq, dtype=np.uint64).astype(np.uint32)
     q["max_samples"] = rng.choice([0, 1, 5, 9, 33, 500, 5000, 30000], nq)
-    return dict(lx=lx, ly=ly, res=res_m, density=density, mseed=mseed, moved=moved), g, master, ref, q
+    # (drawn last: the maps and queries of a seed are the ones they were before these two existed)
+    form = "device" if rng.random() < 0.3 else "host"
+    max_path_len = int(rng.choice([2048, 2048, 64, 8, 3, 1]))        # the short ones cut paths: path_len stays the full length
+    return dict(lx=lx, ly=ly, res=res_m, density=density, mseed=mseed, moved=moved, form=form, max_path_len=max_path_len), g, master, ref, q
 
 
 def engine_for(info, g, master, ref):
@@ -77,8 +82,9 @@ def repro(seed, case, k):
 
 
 def first_divergence(info, g, master, ref, q, k):
-    """binary search over the sample budget for the first sample GPU and oracle decide differently, then a CPU
-    replica of the oracle up to that sample.  Returns True when the two nearest tree nodes of that sample -- or of an
+    """The developer's tool for reading a mismatch main() reported (main() itself excuses nothing): binary search over the
+    sample budget for the first sample GPU and oracle decide differently, then a CPU replica of the oracle (the reference's
+    atan2 / cos / sin steering) up to that sample.  Returns True when the two nearest tree nodes of that sample -- or of an
     earlier one: sample and node counts can coincide again after the trees diverged -- are within 2 ulp of each other,
     or when the blocked-disc test of a steered node hinges on an occupied cell whose centre lies within a few ulp of the
     disc's edge: ties the last bit of atan2 / cos / sin (device libm vs glibc) decides -- see DESIGN.md 4."""
@@ -193,34 +199,60 @@ def first_divergence(info, g, master, ref, q, k):
     return near_tie or tie_at is not None or disc_at is not None
 
 
+SENTINEL = 0xA5
+
+
+def sentinel_paths(n, max_path_len):
+    return np.full(n * max_path_len * 16, SENTINEL, np.uint8).view(np.float64).reshape(n, max_path_len, 2)
+
+
+def engine_answer(info, e, q):
+    """(results, paths) of the batch through the host or the device form, the paths array sentinel-filled beforehand"""
+    n, mpl = len(q), info["max_path_len"]
+    if info["form"] == "host":
+        return e.rrt(q, mpl, paths=sentinel_paths(n, mpl))
+    d_q = torch.from_numpy(q.view(np.uint8).copy()).cuda()
+    d_paths = torch.full((n * mpl * 16,), SENTINEL, dtype=torch.uint8, device="cuda")
+    d_res = torch.full((n * 16,), SENTINEL, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    e.rrt_device(d_q.data_ptr(), n, d_paths.data_ptr(), mpl, d_res.data_ptr())
+    e.synchronize()
+    return d_res.cpu().numpy().view(R.capi.RRT_RESULT_DTYPE), d_paths.cpu().numpy().view(np.float64).reshape(n, mpl, 2)
+
+
 def main():
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     rng = np.random.default_rng(seed)
     t_end = time.time() + budget
-    cases = queries = reached = aborted = libm_ties = 0
+    cases = queries = reached = aborted = full = device = cut = 0
     while time.time() < t_end:
         info, g, master, ref, q = gen_case(rng)
         e = engine_for(info, g, master, ref)
-        res, paths = e.rrt(q)
+        res, paths = engine_answer(info, e, q)
+        mpl = info["max_path_len"]
         for k in range(len(q)):
             ores, opath = oracle_plan(g, ref, q, k)
             got = (int(res["status"][k]), int(res["tree_size"][k]), int(res["samples"][k]), int(res["path_len"][k]))
             want = (ores.status, ores.tree_size, ores.samples, ores.path_len)
-            if got != want or not np.allclose(paths[k, :ores.path_len], opath, rtol=0, atol=1e-9):
-                print("MISMATCH", info, "repro: %d %d %d" % (seed, cases, k), "gpu", got, "oracle", want)
-                if got[:3] != want[:3] and int(q["max_samples"][k]) > 0 and first_divergence(info, g, master, ref, q, k):
-                    print("-> a nearest-node tie within 2 ulp or a disc-edge cell within a few ulp (libm last bit): counted, not a failure")
-                    libm_ties += 1
-                    continue
+            row = sentinel_paths(1, mpl)[0]
+            w = min(ores.path_len, mpl)
+            row[:w] = opath[:w]
+            if got != want or paths[k].tobytes() != row.tobytes():
+                print("MISMATCH", info, "repro: %d %d %d" % (seed, cases, k), "gpu", got, "oracle", want,
+                      "way points equal" if np.array_equal(paths[k, :w], opath[:w]) else "way points differ",
+                      "rest of the row untouched" if (paths[k, w:].view(np.uint8) == SENTINEL).all() else "written behind the way points")
                 sys.exit(1)
             reached += ores.status == 1
             aborted += ores.status == -1
+            full += ores.status == 0
+            cut += ores.path_len > mpl
         queries += len(q)
         cases += 1
+        device += info["form"] == "device"
         e.close()
-    print("rrt fuzz ok: %d maps, %d queries (%d reached, %d out of budget; %d diverged at a last-bit tie: nearest node or disc edge) in %.0f s, seed %d"
-          % (cases, queries, reached, aborted, libm_ties, budget, seed))
+    print("rrt fuzz ok: %d maps (%d through the device form), %d queries (%d reached, %d tree full, %d out of budget; %d paths cut by "
+          "max_path_len) in %.0f s, seed %d" % (cases, device, queries, reached, full, aborted, cut, budget, seed))
 
 
 if __name__ == "__main__":

@@ -7,7 +7,8 @@ map border, poses past the border, for half of the cases one of the VFH paramete
 cells, moved maps (robot radius); sequences of map operations on one engine against the model of tests/_mapmodel.py (map state);
 waypoint graphs of up to 256 vertices and batches of up to 200 queries, a quarter of them held to Dijkstra as well (graph A*);
 occupancy-grid conversions and LaserScan batches of unlike scans through the host and the device forms, every end point held to the
-accepted-value rule of tests/_scan_reference.py (messages).
+accepted-value rule of tests/_scan_reference.py (messages); RRT on maps of 4-30 m at 0.025-0.2 m, moved or not, through the host and
+the device form, with max_path_len above and below the paths, bit for bit against oracle/rrt.c in the kernel's formulation (RRT).
 A fuzzer exits non-zero at the first difference from the oracle
 and prints the configuration that reproduces it.  The search kernel's correctness rests on an asynchronous scheduler,
 `asm volatile` fences and on what the optimiser may hoist: this net catches what the hand-picked cases do not."""
@@ -77,3 +78,16 @@ def test_fuzz_msgs_fixed_seed():
     # a map also costs an engine, its uploads and the launches.
     assert maps >= 30, text
     assert int(text.split("(")[1].split("batches through the device form")[0]) >= 10, text
+
+
+def test_fuzz_rrt_fixed_seed():
+    text = run_fuzzer("fuzz_rrt.py", 10, 309)
+    maps = int(text.split("fuzz ok:")[1].split("maps")[0])
+    # What a case costs is the oracle (budgets up to 30 000 samples a query).  Measured on a CPU-only machine with the engine's
+    # answers replaced by the oracle's own (so the oracle side ran twice): 25 maps and 310 queries in 10 s with this seed (39 and
+    # 32 maps with seeds 1 and 2).  The floor is below half of that: the GPU host's CPUs are shared, and there a map also costs
+    # an engine, its uploads and the launch.  The first 8 maps of this seed hold 5 device-form batches, 4 moved maps and 4 values
+    # of max_path_len below the paths.
+    assert maps >= 8, text
+    assert int(text.split("maps (")[1].split("through the device form")[0]) >= 3, text
+    assert int(text.split("out of budget;")[1].split("paths cut")[0]) >= 1, text

@@ -11,6 +11,7 @@ import pytest
 
 import _oracle as O
 from _gpu import Hip, R, bits, check_scan_rays, same_f32  # noqa: F401  (R: the fixture)
+from _rrt_cases import check_rrt_query
 
 pytestmark = pytest.mark.gpu
 
@@ -345,27 +346,6 @@ def oracle_pool(fn, n):
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max(1, min(32, len(os.sched_getaffinity(0))))) as ex:
         return list(ex.map(fn, range(n)))
-
-
-def check_rrt_query(res, paths, q, k, g, master, tol=0.2):
-    """One RRT query of a batch against oracle/rrt.c, BOTH formulations of extendTree's steering step
-    (/root/reference/move_control/src/rrt_planner.cpp:43-51):
-      steer = 1  the kernel's own (near + 0.4 (dx, dy) / sqrt(dx^2 + dy^2), IEEE operations only): status, tree size, samples,
-                 path length and every way point bit for bit;
-      steer = 0  the REFERENCE's (a = atan2(dy, dx); near + 0.4 (cos a, sin a), this libc's libm): the same counts exactly and
-                 every way point within 1e-9 m -- the device-side check against the reference's formulation (the one round 5
-                 dropped).  A last-bit tie can in principle part the two trees (scripts/fuzz_rrt.py: 4 in 1.9e5 queries, none
-                 on any map the tests use), so a test that meets one names it instead of loosening this."""
-    args = dict(tol=tol, seed=int(q["seed"][k]), max_samples=int(q["max_samples"][k]))
-    ores, opath = O.rrt_plan(g, master, tuple(q["start"][k]), tuple(q["target"][k]), steer=1, **args)
-    got = (res["status"][k], res["tree_size"][k], res["samples"][k], res["path_len"][k])
-    assert got == (ores.status, ores.tree_size, ores.samples, ores.path_len), (k, "steer=1")
-    assert np.array_equal(paths[k, :ores.path_len], opath), (k, "steer=1")
-    rres, rpath = O.rrt_plan(g, master, tuple(q["start"][k]), tuple(q["target"][k]), steer=0, **args)
-    assert got == (rres.status, rres.tree_size, rres.samples, rres.path_len), (k, "steer=0: the reference's atan2 / cos / sin")
-    if rres.path_len:
-        assert np.abs(paths[k, :rres.path_len] - rpath).max() < 1e-9, (k, "steer=0 way points")
-    return ores.status
 
 
 def check_astar(R, e, master, queries, max_len, settled_counts=True, **cfg):

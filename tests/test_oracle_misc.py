@@ -224,7 +224,7 @@ def test_rrt_steering_formulations_part_only_in_the_last_bits():
     sin a), this libc's libm; /root/reference/move_control/src/rrt_planner.cpp:43-51) and as the HIP kernel computes it
     (near + 0.4 (dx, dy) / sqrt(dx^2 + dy^2): IEEE operations only -- no device libm reproduces glibc's atan2 / cos / sin bit for
     bit, and the three calls held the kernel at 127 VGPRs).  The GPU tests compare the kernel with the second one bit for bit AND
-    with the first one at 1e-9 m (tests/test_gpu_parity.py::check_rrt_query); this test is the bridge between the two on the
+    with the first one at 1e-9 m (tests/_rrt_cases.py::check_rrt_query); this test is the bridge between the two on the
     CPU, at BASELINE config 4's own size: its map (2048 x 2048, 30 % rectangles, seed 3), one GPU's share of 512 queries, the
     100 000-sample budget.  EVERY tree has the same status, size, sample count and path length under both formulations and no
     way point differs by more than 1e-12 m (measured: 1.4e-14).  A one-ulp difference CAN flip a later nearest-node or
