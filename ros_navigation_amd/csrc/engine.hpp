@@ -12,10 +12,11 @@
 #include "gridmath.hpp"
 #include "map_state.hpp"
 
-// control words of the goal field and of the frontiers: each private to its file (defined in its unnamed namespace)
+// control words of the goal field and of the frontiers, the VFH+ kernels' argument: each private to its file (defined in its unnamed namespace)
 namespace {
 struct GfCtl;
 struct FrCtl;
+struct VfhK;
 }  // namespace
 
 namespace rna {
@@ -48,22 +49,11 @@ struct HimmScratch {
 struct VfhDevice {
   bool ready = false;
   rna_vfh_params p{};
-  int n_robots = 0;
-  int W = 0, H = 0, T = 0, CX = 0, CY = 0, NQ = 0, NQF = 0, NW = 0, max_speed = 0;
-  // tables
-  float *cell_dist = nullptr, *cell_base_mag = nullptr, *cell_dir = nullptr;  // [q] in (y outer, x inner) order
-  int* range_idx = nullptr;        // [q] rint(2*dir)
-  unsigned* memb = nullptr;        // [T][H][NW] sector-major membership bit masks over q
-  unsigned* in_circle = nullptr;   // [max_speed+1][2][NW] cell inside right / left blocked circle
-  int* min_turning_radius = nullptr;  // [max_speed+1]
-  // per-robot state
-  float *last_binary = nullptr, *hist = nullptr, *origin = nullptr;
-  float *picked = nullptr, *last_picked = nullptr, *blocked_radius = nullptr;
-  int* last_chosen_speed = nullptr;
-  // staging
-  rna_pose* poses_dev = nullptr;
-  rna_vfh_out* out_dev = nullptr;
-  double* ranges_dev = nullptr;
+  int n_robots = 0, H = 0;
+  char *tables = nullptr, *state = nullptr;   // the two device blocks, laid out by VfhLayout (vfh_tables.hpp)
+  float *hist = nullptr, *origin = nullptr;   // [n_robots][H] of the state block (msgs.hip reads them)
+  VfhK* k = nullptr;                          // the kernels' argument, filled once by rna_vfh_init (host memory, vfh.hip)
+  rna_pose* poses_dev = nullptr; rna_vfh_out* out_dev = nullptr; double* ranges_dev = nullptr;   // staging of the host forms, allocated at their first call
 };
 
 // One pipeline stage of the grid A* (astar.hip owns it; astar_tile.hip lays out its blocks and launches on its stream).

@@ -18,20 +18,13 @@
 // All tables that need libm (atanf, asinf, pow, tan, hypotf) are built on the host at init with the
 // same calls the reference makes, so the device never re-derives them.
 #include "engine.hpp"
-
-#include <cmath>
-#include <cstring>
-#include <vector>
+#include "vfh_tables.hpp"
 
 using namespace rna;
 
 namespace {
 
 constexpr int VFH_THREADS = 128;
-constexpr int MAX_W = 64;
-constexpr int MAX_NQ = (MAX_W / 2 + 1) * MAX_W;   // 2112
-[[maybe_unused]] constexpr int MAX_NW = (MAX_NQ + 31) / 32;        // 66 (the kernel sizes its LDS by the actual window)
-constexpr int MAX_H = 128;
 constexpr int VFH_OCC_CAP = 1024;
 
 struct VfhK {
@@ -46,26 +39,6 @@ struct VfhK {
   float *last_binary, *hist, *origin, *picked, *last_picked, *blocked_radius;
   int *last_chosen_speed, *max_speed_picked;
 };
-
-// ---- small pieces of vfh.cpp that are pure arithmetic (usable on host and device) --------------
-RNA_HD int k_max_turnrate(int mt0, int mt1, int speed) {  // vfh.cpp:130-138
-  int val = (mt0 - (int)(speed * (mt0 - mt1) / 1000.0));
-  return val < 0 ? 0 : val;
-}
-RNA_HD int k_safety_dist(float sd0, float sd1, int speed) {  // vfh.cpp:194-205
-  int val = (int)(sd0 + (int)(speed * (sd1 - sd0) / 1000.0));
-  return val < 0 ? 0 : val;
-}
-RNA_HD float k_delta_angle(float a1, float a2) {  // vfh.cpp:673-686
-  const float diff = a2 - a1;
-  // (both corrections are computed and one value is picked: as an if / else-if the device compiler keeps two nested
-  // branches with their exec-mask bookkeeping at every one of the kernel's twenty call sites)
-  const float down = diff - 360, up = diff + 360;
-  return diff > 180 ? down : (diff < -180 ? up : diff);
-}
-// glibc 2.35 hypotf() is (float)sqrt((double)x*x + (double)y*y); restated so host tables and the
-// device agree bit for bit (checked against libm in tests/test_host_tables.py)
-RNA_HD float k_hypotf(float x, float y) { return (float)sqrt((double)x * (double)x + (double)y * (double)y); }
 
 // angles::normalize_angle_positive (ROS `angles` package)
 // fmod is exact, and for y <= |x| < 2y its value is |x| - y with the sign of x, itself exact (Sterbenz): with |a| < 4 pi --
@@ -716,161 +689,6 @@ __global__ void vfh_reset_kernel(VfhK K, int n) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// host: VFH::VFH + VFH::Init tables (vfh.cpp:53-110,144-166,237-416)
-// ------------------------------------------------------------------------------------------------
-struct HostTables {
-  int W, H, T, CX, CY, YH, NQ, NQF, NW, max_speed;
-  std::vector<float> cell_dist, cell_base_mag, cell_dir;
-  std::vector<int> range_idx;
-  std::vector<unsigned> memb, in_circle;
-  std::vector<int> mtr;
-  std::vector<float> bcr;
-};
-
-float sector_to_dir(float sector, float dir) {  // the four wrap-aware differences of vfh.cpp:343-381
-  if ((sector - dir) > 180) return dir - (sector - 360);
-  if ((dir - sector) > 180) return sector - (dir + 360);
-  return dir - sector;
-}
-
-bool build_tables(const rna_vfh_params& p, HostTables& t) {
-  const float CELL_WIDTH = (float)p.cell_size;
-  const float SD0 = (float)p.safety_dist_0ms, SD1 = (float)p.safety_dist_1ms;
-  const float ROBOT_RADIUS = (float)p.robot_radius;
-  const int W = p.window_diameter, SA = p.sector_angle, MAX_SPEED = p.max_speed;
-  if (W < 2 || W > MAX_W || SA < 1 || MAX_SPEED < 1 || MAX_SPEED > 100000) return false;
-  t.W = W;
-  t.T = (SD0 == SD1) ? 1 : 20;  // vfh.cpp:100-109
-  t.CX = t.CY = (int)floor(W / 2.0);
-  t.H = (int)rint(360.0 / SA);
-  if (t.H < 1 || t.H > MAX_H || t.H != 360 / SA) return false;   // (H 0: a sector angle of 720 and more rounds to no sector at all)
-  // Two sectors that do not close the circle (sector angles 144..179): the second one, at SA degrees, can open, a valley can
-  // end in it, and the reference then closes that valley at -SA + 360 where the kernel's `last * SA` says SA (Select_Direction).
-  if (t.H == 2 && SA != 180) return false;
-  t.YH = (int)ceil(W / 2.0);
-  t.NQ = (t.YH + 1) * W;
-  t.NQF = t.YH * W;
-  t.NW = (t.NQ + 31) / 32;
-  t.max_speed = MAX_SPEED;
-  if (t.YH + 1 > W) return false;
-  const int H = t.H, T = t.T, CX = t.CX, CY = t.CY;
-
-  // Min_Turning_Radius (SetCurrentMaxSpeed, vfh.cpp:144-166) and per-speed blocked circles
-  t.mtr.resize(MAX_SPEED + 1);
-  t.bcr.resize(MAX_SPEED + 1);
-  for (int x = 0; x <= MAX_SPEED; x++) {
-    const double dx = (double)x / 1e6;
-    const double dtheta = ((M_PI / 180) * (double)(k_max_turnrate(p.max_turnrate_0ms, p.max_turnrate_1ms, x))) / 1000.0;
-    t.mtr[x] = (int)(((dx / tan(dtheta)) * 1000.0) * p.min_turn_radius_safety_factor);
-    t.bcr[x] = t.mtr[x] + ROBOT_RADIUS + k_safety_dist(SD0, SD1, x);  // vfh.cpp:1148
-  }
-
-  t.cell_dist.assign(t.NQ, 0.f);
-  t.cell_base_mag.assign(t.NQ, 0.f);
-  t.cell_dir.assign(t.NQ, 0.f);
-  t.range_idx.assign(t.NQ, 0);
-  t.memb.assign((size_t)T * H * t.NW + 16, 0u);   // (+16: the kernel reads sixteen words from a row's start whatever NW is)
-  t.in_circle.assign((size_t)(MAX_SPEED + 1) * 2 * t.NW, 0u);
-
-  for (int x = 0; x < W; x++) {
-    for (int y = 0; y <= t.YH; y++) {
-      const int q = y * W + x;
-      const float dist = (float)(sqrt(pow((double)(CX - x), 2.0) + pow((double)(CY - y), 2.0)) * CELL_WIDTH);
-      const float base = (float)(15 * pow((3000.0 - dist), 4.0) / 100000000.0);
-      float d = 0.0f;
-      if (x < CX) {
-        if (y < CY) { d = atanf((float)(CY - y) / (float)(CX - x)); d = (float)(d * (360.0 / 6.28)); d = (float)(180.0 - d); }
-        else if (y == CY) d = 180.0f;
-        else { d = atanf((float)(y - CY) / (float)(CX - x)); d = (float)(d * (360.0 / 6.28)); d = (float)(180.0 + d); }
-      } else if (x == CX) {
-        d = (y < CY) ? 90.0f : (y == CY ? -1.0f : 270.0f);
-      } else {
-        if (y < CY) { d = atanf((float)(CY - y) / (float)(x - CX)); d = (float)(d * (360.0 / 6.28)); }
-        else if (y == CY) d = 0.0f;
-        else { d = atanf((float)(y - CY) / (float)(x - CX)); d = (float)(d * (360.0 / 6.28)); d = (float)(360.0 - d); }
-      }
-      t.cell_dist[q] = dist;
-      t.cell_base_mag[q] = base;
-      t.cell_dir[q] = d;
-      if (y < t.YH && d < 0) {
-        // The centre cell of an odd window (direction -1) is a front cell: the reference reads laser_ranges[-2] for it, memory
-        // in front of the caller's scan.  Defined here as in oracle/vfh.c: the robot's own cell is never occupied -- a base
-        // magnitude of zero leaves its magnitude zero whatever bin it reads.
-        t.cell_base_mag[q] = 0.f;
-        t.range_idx[q] = 0;
-      } else if (y < t.YH) {
-        const int ri = (int)rint(d * 2.0);  // vfh.cpp:1018
-        if (ri < 0 || ri > 360) return false;  // cannot happen for front cells (y < CY, or y == CY beside the centre of an odd window)
-        t.range_idx[q] = ri;
-      }
-      for (int tb = 0; tb < T; tb++) {
-        const int max_speed_this_table = (int)(((float)(tb + 1) / (float)T) * (float)MAX_SPEED);
-        float enlarge;
-        if (dist > 0) {
-          const float r = ROBOT_RADIUS + k_safety_dist(SD0, SD1, max_speed_this_table);
-          enlarge = (float)((float)asinf(r / dist) * (180 / M_PI));
-        } else {
-          enlarge = 0;
-        }
-        const float plus_dir = d + enlarge, neg_dir = d - enlarge;
-        for (int i = 0; i < (360 / SA); i++) {
-          const float plus_sector = (i + 1) * (float)SA, neg_sector = i * (float)SA;
-          const float nn = sector_to_dir(neg_sector, neg_dir), pn = sector_to_dir(plus_sector, neg_dir);
-          const float pp = sector_to_dir(plus_sector, plus_dir), np = sector_to_dir(neg_sector, plus_dir);
-          bool plus_dir_bw = false, neg_dir_bw = false, around = false;
-          if ((nn >= 0) && (pn <= 0)) neg_dir_bw = true;
-          if ((np >= 0) && (pp <= 0)) plus_dir_bw = true;
-          if ((nn <= 0) && (np >= 0)) around = true;
-          if ((pn <= 0) && (pp >= 0)) plus_dir_bw = true;
-          if (plus_dir_bw || neg_dir_bw || around) t.memb[((size_t)tb * H + i) * t.NW + (q >> 5)] |= 1u << (q & 31);
-        }
-      }
-      if (y < t.YH) {  // blocked-circle membership per speed (vfh.cpp:1140-1189)
-        for (int s = 0; s <= MAX_SPEED; s++) {
-          const float cxr = CX + (t.mtr[s] / (float)CELL_WIDTH);
-          const float cxl = CX - (t.mtr[s] / (float)CELL_WIDTH);
-          const float cy = (float)CY;
-          const float dr = k_hypotf(cxr - x, cy - y) * CELL_WIDTH;
-          const float dl = k_hypotf(cxl - x, cy - y) * CELL_WIDTH;
-          if (dr < t.bcr[s]) t.in_circle[((size_t)s * 2 + 0) * t.NW + (q >> 5)] |= 1u << (q & 31);
-          if (dl < t.bcr[s]) t.in_circle[((size_t)s * 2 + 1) * t.NW + (q >> 5)] |= 1u << (q & 31);
-        }
-      }
-    }
-  }
-  return true;
-}
-
-template <typename T>
-int upload(rna_engine* e, T** dst, const std::vector<T>& src) {
-  int rc = dev_alloc(e, dst, src.size());
-  if (rc != RNA_OK) return rc;
-  RNA_HIP(e, hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, e->stream));
-  return RNA_OK;
-}
-
-VfhK make_k(const rna_engine* e) {
-  const VfhDevice& v = e->vfh;
-  VfhK K{};
-  K.W = v.W; K.H = v.H; K.T = v.T; K.CX = v.CX; K.CY = v.CY; K.YH = v.NQF / v.W; K.NQ = v.NQ; K.NQF = v.NQF;
-  K.NW = v.NW; K.max_speed = v.max_speed; K.sector_angle = v.p.sector_angle;
-  K.cell_width = (float)v.p.cell_size; K.robot_radius = (float)v.p.robot_radius;
-  K.sd0 = (float)v.p.safety_dist_0ms; K.sd1 = (float)v.p.safety_dist_1ms;
-  K.bl0 = (float)v.p.free_space_cutoff_0ms; K.bh0 = (float)v.p.obs_cutoff_0ms;
-  K.bl1 = (float)v.p.free_space_cutoff_1ms; K.bh1 = (float)v.p.obs_cutoff_1ms;
-  K.U1 = (float)v.p.weight_desired_dir; K.U2 = (float)v.p.weight_current_dir;
-  K.current_max_speed = v.p.max_speed; K.max_speed_narrow = v.p.max_speed_narrow_opening;
-  K.max_speed_wide = v.p.max_speed_wide_opening; K.max_accel = v.p.max_acceleration;
-  K.mt0 = v.p.max_turnrate_0ms; K.mt1 = v.p.max_turnrate_1ms;
-  K.cell_dist = v.cell_dist; K.cell_base_mag = v.cell_base_mag; K.cell_dir = v.cell_dir; K.range_idx = v.range_idx;
-  K.memb = v.memb; K.in_circle = v.in_circle; K.mtr = v.min_turning_radius; K.bcr = v.blocked_radius + v.n_robots;
-  K.last_binary = v.last_binary; K.hist = v.hist; K.origin = v.origin; K.picked = v.picked;
-  K.last_picked = v.last_picked; K.blocked_radius = v.blocked_radius; K.last_chosen_speed = v.last_chosen_speed;
-  K.max_speed_picked = v.last_chosen_speed + v.n_robots;
-  return K;
-}
-
 int ensure_staging(rna_engine* e, bool ranges) {
   VfhDevice& v = e->vfh;
   int rc;
@@ -899,7 +717,7 @@ int launch_step(rna_engine* e, const rna_pose* poses_dev, const double* ranges_d
     for (int a = 0; a < 2; ++a)
       if (e->geom.start[a] < 0 || e->geom.start[a] >= e->geom.size[a]) return fail(e, RNA_EINVAL, "vfh: buffer start index outside the map");
     KernelTimer kt(e, RNA_K_VFH_STEP, st);
-    const VfhK K = make_k(e);
+    const VfhK& K = *e->vfh.k;
     const size_t lds = (size_t)(((K.NQ + 31) & ~31) + K.NW) * sizeof(float);   // mag | nz
 #ifdef RNA_VFH_SKIPS
     { const char* sk = getenv("RNA_VFH_SKIP"); const int v = sk ? atoi(sk) : 0; RNA_HIP(e, hipMemcpyToSymbol(HIP_SYMBOL(d_vfh_skip), &v, sizeof v)); }
@@ -916,16 +734,22 @@ int launch_step(rna_engine* e, const rna_pose* poses_dev, const double* ranges_d
   return RNA_OK;
 }
 
+// what the step entry points ask of the engine's state
+int vfh_check(rna_engine* e, int n, const char* who) {
+  if (!e->vfh.ready) return fail(e, RNA_ESTATE, std::string(who) + " before rna_vfh_init");
+  if (n > e->vfh.n_robots) return fail(e, RNA_EINVAL, std::string(who) + ": more poses than VFH instances");
+  return RNA_OK;
+}
+
 }  // namespace
 
 namespace rna {
 int vfh_release(rna_engine* e) {
   VfhDevice& v = e->vfh;
-  dev_free(&v.cell_dist); dev_free(&v.cell_base_mag); dev_free(&v.cell_dir); dev_free(&v.range_idx);
-  dev_free(&v.memb); dev_free(&v.in_circle); dev_free(&v.min_turning_radius);
-  dev_free(&v.last_binary); dev_free(&v.hist); dev_free(&v.origin); dev_free(&v.picked); dev_free(&v.last_picked);
-  dev_free(&v.blocked_radius); dev_free(&v.last_chosen_speed);
+  dev_free(&v.tables); dev_free(&v.state);
   dev_free(&v.poses_dev); dev_free(&v.out_dev); dev_free(&v.ranges_dev);
+  delete v.k;
+  v.k = nullptr; v.hist = v.origin = nullptr;
   v.ready = false;
   return RNA_OK;
 }
@@ -953,30 +777,28 @@ extern "C" int rna_vfh_init(rna_engine* e, const rna_vfh_params* p, int n_robots
   vfh_release(e);
   VfhDevice& v = e->vfh;
   v.p = *p;
-  v.n_robots = n_robots;
-  v.W = t.W; v.H = t.H; v.T = t.T; v.CX = t.CX; v.CY = t.CY; v.NQ = t.NQ; v.NQF = t.NQF; v.NW = t.NW;
-  v.max_speed = t.max_speed;
-  int rc;
-  if ((rc = upload(e, &v.cell_dist, t.cell_dist)) != RNA_OK) return rc;
-  if ((rc = upload(e, &v.cell_base_mag, t.cell_base_mag)) != RNA_OK) return rc;
-  if ((rc = upload(e, &v.cell_dir, t.cell_dir)) != RNA_OK) return rc;
-  if ((rc = upload(e, &v.range_idx, t.range_idx)) != RNA_OK) return rc;
-  if ((rc = upload(e, &v.memb, t.memb)) != RNA_OK) return rc;
-  if ((rc = upload(e, &v.in_circle, t.in_circle)) != RNA_OK) return rc;
-  if ((rc = upload(e, &v.min_turning_radius, t.mtr)) != RNA_OK) return rc;
-  const size_t nh = (size_t)n_robots * t.H;
-  if ((rc = dev_alloc(e, &v.last_binary, nh)) != RNA_OK) return rc;
-  if ((rc = dev_alloc(e, &v.hist, nh)) != RNA_OK) return rc;
-  if ((rc = dev_alloc(e, &v.origin, nh)) != RNA_OK) return rc;
-  if ((rc = dev_alloc(e, &v.picked, (size_t)n_robots)) != RNA_OK) return rc;
-  if ((rc = dev_alloc(e, &v.last_picked, (size_t)n_robots)) != RNA_OK) return rc;
-  // blocked_radius: [n_robots] per-robot state followed by the [max_speed+1] per-speed table
-  if ((rc = dev_alloc(e, &v.blocked_radius, (size_t)n_robots + t.bcr.size())) != RNA_OK) return rc;
-  RNA_HIP(e, hipMemcpyAsync(v.blocked_radius + n_robots, t.bcr.data(), t.bcr.size() * sizeof(float),
-                            hipMemcpyHostToDevice, e->stream));
-  // last_chosen_speed: [n_robots] followed by Max_Speed_For_Picked_Angle [n_robots]
-  if ((rc = dev_alloc(e, &v.last_chosen_speed, (size_t)2 * n_robots)) != RNA_OK) return rc;
-  RNA_HIP(e, hipStreamSynchronize(e->stream));  // host vectors go out of scope
+  v.n_robots = n_robots; v.H = t.H;
+  const VfhLayout L(t, (size_t)n_robots);
+  int rc = dev_alloc(e, &v.tables, L.table_bytes);
+  if (rc == RNA_OK) rc = dev_alloc(e, &v.state, L.state_bytes);
+  if (rc != RNA_OK) { vfh_release(e); return rc; }
+  RNA_HIP(e, hipMemcpyAsync(v.tables, t.block.data(), L.table_bytes, hipMemcpyHostToDevice, e->stream));
+  // the kernels' argument: nothing in it changes until the next init
+  VfhK& K = *(v.k = new VfhK{});
+  K.W = t.W; K.H = t.H; K.T = t.T; K.CX = t.CX; K.CY = t.CY; K.YH = t.YH; K.NQ = t.NQ; K.NQF = t.NQF; K.NW = t.NW; K.max_speed = t.max_speed;
+  K.sector_angle = p->sector_angle; K.cell_width = (float)p->cell_size; K.robot_radius = (float)p->robot_radius;
+  K.sd0 = (float)p->safety_dist_0ms; K.sd1 = (float)p->safety_dist_1ms; K.U1 = (float)p->weight_desired_dir; K.U2 = (float)p->weight_current_dir;
+  K.bl0 = (float)p->free_space_cutoff_0ms; K.bh0 = (float)p->obs_cutoff_0ms; K.bl1 = (float)p->free_space_cutoff_1ms; K.bh1 = (float)p->obs_cutoff_1ms;
+  K.current_max_speed = p->max_speed; K.max_speed_narrow = p->max_speed_narrow_opening; K.max_speed_wide = p->max_speed_wide_opening;
+  K.max_accel = p->max_acceleration; K.mt0 = p->max_turnrate_0ms; K.mt1 = p->max_turnrate_1ms;
+  place(K.cell_dist, v.tables, L.cell_dist); place(K.cell_base_mag, v.tables, L.cell_base_mag); place(K.cell_dir, v.tables, L.cell_dir);
+  place(K.range_idx, v.tables, L.range_idx); place(K.memb, v.tables, L.memb); place(K.in_circle, v.tables, L.in_circle);
+  place(K.mtr, v.tables, L.min_turning_radius); place(K.bcr, v.tables, L.bcr);
+  place(K.last_binary, v.state, L.last_binary); place(K.hist, v.state, L.hist); place(K.origin, v.state, L.origin);
+  place(K.picked, v.state, L.picked); place(K.last_picked, v.state, L.last_picked); place(K.blocked_radius, v.state, L.blocked_radius);
+  place(K.last_chosen_speed, v.state, L.last_chosen_speed); place(K.max_speed_picked, v.state, L.max_speed_picked);
+  v.hist = K.hist; v.origin = K.origin;
+  RNA_HIP(e, hipStreamSynchronize(e->stream));  // the host tables go out of scope
   v.ready = true;
   return rna_vfh_reset(e);
 }
@@ -987,7 +809,7 @@ extern "C" int rna_vfh_reset(rna_engine* e) {
   RNA_ENTER(e);
   const int n = e->vfh.n_robots;
   const int threads = n * e->vfh.H;
-  hipLaunchKernelGGL(vfh_reset_kernel, dim3((threads + 255) / 256), dim3(256), 0, e->stream, make_k(e), n);
+  hipLaunchKernelGGL(vfh_reset_kernel, dim3((threads + 255) / 256), dim3(256), 0, e->stream, *e->vfh.k, n);
   RNA_HIP(e, hipGetLastError());
   RNA_HIP(e, hipStreamSynchronize(e->stream));
   return RNA_OK;
@@ -998,8 +820,7 @@ extern "C" int rna_vfh_hist_size(const rna_engine* e) { return (e && e->vfh.read
 extern "C" int rna_vfh_step_batch_device(rna_engine* e, const rna_pose* poses, int n, rna_vfh_out* out,
                                          float* origin_hist, float* hist) {
   if (!e || !poses || !out || n < 0) return RNA_EINVAL;
-  if (!e->vfh.ready) return fail(e, RNA_ESTATE, "rna_vfh_step_batch before rna_vfh_init");
-  if (n > e->vfh.n_robots) return fail(e, RNA_EINVAL, "more poses than VFH instances");
+  if (const int rc = vfh_check(e, n, "rna_vfh_step_batch_device")) return rc;
   if (n == 0) return RNA_OK;
   RNA_ENTER_NOJOIN(e);   // (steps on the VFH+ stream follow one another there)
   // next to pipelined searches the step runs on its own stream: it only reads the master layer and the robots' state
@@ -1009,13 +830,11 @@ extern "C" int rna_vfh_step_batch_device(rna_engine* e, const rna_pose* poses, i
 static int step_host(rna_engine* e, const double* ranges_host, const rna_pose* poses_host, int n,
                      rna_vfh_out* out_host, float* origin_host, float* hist_host) {
   if (!e || !poses_host || !out_host || n < 0) return RNA_EINVAL;
-  if (!e->vfh.ready) return fail(e, RNA_ESTATE, "VFH step before rna_vfh_init");
-  VfhDevice& v = e->vfh;
-  if (n > v.n_robots) return fail(e, RNA_EINVAL, "more poses than VFH instances");
-  if (n == 0) return RNA_OK;
+  int rc = vfh_check(e, n, ranges_host ? "rna_vfh_update_batch" : "rna_vfh_step_batch");
+  if (rc != RNA_OK || n == 0) return rc;
   RNA_ENTER(e);
-  int rc = ensure_staging(e, ranges_host != nullptr);
-  if (rc != RNA_OK) return rc;
+  VfhDevice& v = e->vfh;
+  if ((rc = ensure_staging(e, ranges_host != nullptr)) != RNA_OK) return rc;
   RNA_HIP(e, hipMemcpyAsync(v.poses_dev, poses_host, (size_t)n * sizeof(rna_pose), hipMemcpyHostToDevice, e->stream));
   if (ranges_host)
     RNA_HIP(e, hipMemcpyAsync(v.ranges_dev, ranges_host, (size_t)n * 361 * 2 * sizeof(double), hipMemcpyHostToDevice,

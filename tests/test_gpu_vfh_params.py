@@ -131,6 +131,20 @@ def test_second_init_with_another_sector_count(R):
     e.close()
 
 
+@pytest.mark.parametrize("n", [1, 3])
+@pytest.mark.parametrize("name", ["sa360", "sa8", "w2"])
+def test_few_robots_keep_their_state_apart(R, name, n):
+    """one and three robots at H 1, 45 and 72: the per-robot arrays are 4 to 864 bytes and lie side by side in the state block, so
+    an overlap or a swapped offset changes a histogram at the second step; before and after a reset"""
+    seqs, want = V.sequences(name)[:n], V.oracle_answers(name)[:n]
+    e = R.Engine(4.0, 4.0, 0.05)
+    e.vfh_init(n, V.capi_params(R, V.params(name)))
+    run_engine(R, e, seqs, want, name, steps=range(6))
+    e.vfh_reset()
+    run_engine(R, e, seqs, want, name + " after reset", steps=range(6))
+    e.close()
+
+
 def test_partial_batches_leave_the_other_robots_alone(R):
     """stepping the first m robots leaves the others' state untouched: they answer later as oracles that skipped those steps"""
     name = "cut"
